@@ -6,7 +6,19 @@ timed region.  One step = fbank + CMN + ECAPA forward + embedding for the whole
 batch, all in libwsp_hip.so.  Multi-GPU: one rank per GPU (torchrun), each
 rank extracts its own shard (weak scaling, no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: build the workload,
+W warm-up steps, K timed steps (per-kernel-class HIP events ride inside the
+timed region), one JSON line.  `--full` adds every side measurement to the same
+line: `value_sustained`, `value_exact_f32`, the dominant kernel's standalone
+roofline pass, C4's batch-64 figure, the CPU baselines, the `configs` sub-records
+(C3, C4, C5) and, with more than one rank, the RCCL all-reduce check; the
+`--no-*`, `--sustain-seconds` and `--configs` options trim a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left in the step's output
+buffers (`feats`, `emb`) as float32 `DIR/<name>.npy` (see dump_outputs); inputs
+and weights are seeded, so two builds can be compared array for array.
 
 `--gpus N` without a torchrun environment starts N ranks itself (torchrun as a
 child process, before anything touches the GPU) and relays rank 0's line;
@@ -229,6 +241,12 @@ def parse():
     ap.add_argument("--arch", default="ECAPA_TDNN_c1024",
                     help=f"ECAPA_TDNN_*, ResNet*, or {HUBERT_ARCH} (wav -> HuBERT -> CMN -> ECAPA)")
     ap.add_argument("--seconds", type=float, default=5.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (sustained window, exact f32, standalone kernel roofline, "
+                         "C4 batch 64, CPU baselines, the --configs sub-records, the multi-rank all-reduce check); "
+                         "the options below that trim them apply to --full runs only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (feats, emb) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--precision", type=int, default=1, help="1 = bf16x3 split MFMA, 0 = f32 MFMA")
@@ -768,6 +786,27 @@ def gflop_per_utt(w) -> float:
     return resnet_gflop_per_utt(spec, T)
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # all arrays of one --dump-outputs call together (the files stay under 64 MB)
+
+
+def dump_outputs(dirname: str, arrays, rank: int) -> None:
+    """--dump-outputs: each (name, device tensor) as float32 `dirname/<name>.npy` (ranks
+    above 0: `<name>.rank<r>.npy`), smallest first.  An array that does not fit what is
+    left of DUMP_BUDGET_BYTES is written as a fixed sample of its rows (the last axis
+    kept whole; row indices drawn once from default_rng(0), ascending), the same rows on
+    every run of the same shape."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in sorted(arrays, key=lambda nt: nt[1].numel()):
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.nbytes > left:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = min(rows.shape[0], left // (4 * rows.shape[1]))
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
 def run_workload(args, arch: str, B: int, steps: int, warmup: int, world: int, rank: int, dev, dist,
                  headline: bool, cpu_seconds: float) -> dict:
     """One workload: W untimed warm-up steps, then K steps timed between barrier +
@@ -809,6 +848,9 @@ def run_workload(args, arch: str, B: int, steps: int, warmup: int, world: int, r
                 mm.profile(False)
     el = max_over_ranks(el)
     value = world * B * steps / el
+    if headline and args.dump_outputs:
+        # before any side measurement reuses the buffers: what the last timed step wrote
+        dump_outputs(args.dump_outputs, [("feats", w["feats"]), ("emb", w["emb"])], rank)
 
     def timed(n):
         barrier()
@@ -926,6 +968,12 @@ def main():
         sys.exit(launch_ranks(args.gpus))
     if args.plumbing:
         return plumbing_main(args)
+    if not args.full:
+        # a plain run: the headline's own warm-up and timed steps only
+        args.no_cpu_baseline = args.no_f32 = args.no_kernel_roofline = True
+        args.hubert_small_batch = False
+        args.sustain_seconds = 0.0
+        args.configs = "none"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -997,7 +1045,7 @@ def main():
     # compact per-config summary, LAST key of the line (the driver keeps only the tail of
     # stdout): value, step time, whole-model roofline fraction, dominant-kernel fraction, CPU
     res["summary"] = summarize(res)
-    if dist is not None:
+    if dist is not None and args.full:
         # untimed: the AS-Norm cohort-statistics all-reduce (dist.allreduce_sums, one fused
         # f64 buffer over RCCL/xGMI, score_norm.py's cohort means) on this run's ranks,
         # checked against its closed form -- the one collective of the extraction path

@@ -19,7 +19,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for arm in ${ARMS:-default}; do
     opts=""
     if [ "$arm" != "default" ]; then for kv in ${arm//,/ }; do opts="$opts --opt $kv"; done; fi
-    timeout -k 10 300 python -u bench.py --arch $ARCH --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-f32 \
+    timeout -k 10 300 python -u bench.py --full --arch $ARCH --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-f32 \
       --configs none --sustain-seconds 2 --no-kernel-roofline --no-hubert-b64 $opts \
       > gpurun_out/ab.json 2> gpurun_out/ab.err || { tail -20 gpurun_out/ab.err; exit 1; }
     python -c "

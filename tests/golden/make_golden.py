@@ -121,9 +121,19 @@ def make_models(out, only=None):
                    param_shapes=np.array([",".join(map(str, v.shape)) for v in model.state_dict().values()]),
                    embed=emb.numpy().astype(np.float32))
         if inter:
-            # channels-first (B,C,T) as the reference produces; keep only batch 0
+            # channels-first (B,C,T) as the reference produces; keep only batch 0.  The frame-level
+            # ones go beside the fixture as <name>_inter/<layer>[_<i>].npy, one file per block of
+            # <= 512 channels (each file stays well under 1 MiB)
+            os.makedirs(os.path.join(out, name + "_inter"), exist_ok=True)
             for k, v in inter.items():
-                rec["inter_" + k] = v[:1].astype(np.float32)
+                v = v[:1].astype(np.float32)
+                if v.ndim != 3:
+                    rec["inter_" + k] = v
+                    continue
+                parts = [v[:, c:c + 512] for c in range(0, v.shape[1], 512)]
+                for i, p in enumerate(parts):
+                    np.save(os.path.join(out, name + "_inter", k + (f"_{i}" if len(parts) > 1 else "") + ".npy"),
+                            np.ascontiguousarray(p))
         np.savez_compressed(os.path.join(out, name + ".npz"), **rec)
         print(name, emb.shape, float(emb.abs().max()), float(emb.std()))
 

@@ -37,6 +37,32 @@ def test_bench_single_rank_default():
     assert res["n_gpus"] == 1 and res["config"]["parallelism"] == "dp1"
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array; an array over the byte budget is a fixed
+    ascending sample of whole rows, the same rows on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    emb = torch.arange(6 * 4, dtype=torch.float64).reshape(6, 4)
+    feats = torch.arange(6 * 50 * 8, dtype=torch.float32).reshape(6, 50, 8)
+    bench.dump_outputs(str(tmp_path / "a"), [("feats", feats), ("emb", emb)], 0)
+    e, f = np.load(tmp_path / "a" / "emb.npy"), np.load(tmp_path / "a" / "feats.npy")
+    assert e.dtype == np.float32 and f.dtype == np.float32
+    assert np.array_equal(e, emb.numpy()) and np.array_equal(f, feats.numpy())
+    # budget: emb whole (96 B) + 100 of the 300 feats rows (32 B each)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 96 + 100 * 32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), [("feats", feats), ("emb", emb)], 1)
+    e, f = np.load(tmp_path / "b" / "emb.rank1.npy"), np.load(tmp_path / "b" / "feats.rank1.npy")
+    assert np.array_equal(e, emb.numpy())
+    assert f.shape == (100, 8) and e.nbytes + f.nbytes <= 96 + 100 * 32
+    rows = feats.numpy().reshape(-1, 8)
+    idx = (f[:, 0] // 8).astype(int)  # row r starts at value 8 r
+    assert np.all(np.diff(idx) > 0) and np.array_equal(f, rows[idx])
+    assert np.array_equal(f, np.load(tmp_path / "c" / "feats.rank1.npy"))
+
+
 def test_bench_world_mismatch_is_an_error():
     env = {k: v for k, v in os.environ.items()}
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

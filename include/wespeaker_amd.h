@@ -131,7 +131,13 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
 /* arch: "ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
  * "ECAPA_TDNN_GLOB_c1024", "ResNet18/34/50/101/152/221/293"
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
- * "HuBERT_base" (embed_dim 768; wespeaker/frontend/s3prl.py:23-75). */
+ * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
+ * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /
+ * wavlm_base_plus: HuBERT-base with a gated relative-position bias in every
+ * attention; next to HuBERT_base's parameters it takes, per encoder layer,
+ * self_attn.grep_linear.{weight (8, 64), bias (8)} and self_attn.grep_a (1, 12, 1, 1),
+ * and in layer 0 self_attn.relative_attention_bias.weight (320, 12).  Every
+ * "HuBERT front end" option and the wsp_frontend_* calls apply to both. */
 int wsp_model_create(const char* arch, int feat_dim, int embed_dim, int emb_bn,
                      int two_emb_layer, wsp_model** out);
 int wsp_model_destroy(wsp_model* m);
@@ -203,7 +209,8 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block
- *                  per (utterance, head, 128-query block); both bf16x3 MFMA
+ *                  per (utterance, head, 128-query block); both bf16x3 MFMA, both with WavLM's
+ *                  gated relative-position bias on a WavLM_base handle
  *   "pos_conv"     HuBERT front end, precision 1: 1 = the positional conv as a direct grouped
  *                  conv (pos_conv.hip: one block per 256 frames x group, input patch split into
  *                  bf16 hi / lo once in LDS; default), 0 = the grouped implicit GEMM (48 of 64
@@ -240,7 +247,8 @@ int wsp_model_profile_query(wsp_model* m, const char* kernel_class, int* launche
  * states, or the single state chosen with wsp_model_set_option(m, "layer", k)
  * before finalize) -> s3prl length match, optionally followed by
  * bin/extract.py:104-106's apply_cmvn (cmn = 1).  Handles come from
- * wsp_model_create("HuBERT_base", 1, 768, 0, 0, &m); parameters are the
+ * wsp_model_create("HuBERT_base", 1, 768, 0, 0, &m) or, for WavLM Base / Base+,
+ * wsp_model_create("WavLM_base", 1, 768, 0, 0, &m); parameters are the
  * reference checkpoint's "frontend.*" entries. */
 /* Frames per utterance: len(range(0, num_samples, 320)). num_samples >= 1; inputs
  * shorter than 800 samples run zero-padded to 800 (s3prl MIN_SECOND = 0.05 s). */

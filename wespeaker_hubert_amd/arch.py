@@ -304,3 +304,49 @@ def hubert_gflop_per_utt(num_samples: int, cfg=HUBERT_BASE) -> float:
     macs += t * h * (h // cfg["pos_groups"]) * cfg["pos_k"]         # grouped pos_conv
     per_layer = t * h * 3 * h + 2 * t * t * h + t * h * h + 2 * t * h * cfg["ffn"]
     return 2.0 * (macs + L * per_layer) / 1e9
+
+
+# ----------------------------------------------------------------- WavLM ---
+# s3prl `wavlm_base` / `wavlm_base_plus`: HuBERT-base in every shape, plus a gated, bucketed
+# relative-position bias on every attention score (published WavLM source; transformers' WavLMModel
+# is the offline proxy).  Layer 0 owns the bucket embedding, every layer its own gate.
+WAVLM_BASE = dict(HUBERT_BASE, rel_buckets=320, rel_max_distance=800, gate_dim=8)
+WAVLM_UPSTREAMS = ("wavlm_base", "wavlm_base_plus")
+
+
+def wavlm_params(cfg=WAVLM_BASE, prefix: str = HUBERT_PREFIX) -> ParamList:
+    """hubert_params() with, behind each layer's final_layer_norm, the layer's gate
+    (grep_linear, grep_a) and, in layer 0, relative_attention_bias.weight (buckets, heads)."""
+    H = cfg["heads"]
+    dh = cfg["hidden"] // H
+    out: ParamList = []
+    for name, shape in hubert_params(cfg, prefix):
+        out.append((name, shape))
+        if name.endswith(".final_layer_norm.bias"):
+            p = name[:-len("final_layer_norm.bias")] + "self_attn."
+            if ".layers.0." in name:
+                out.append((p + "relative_attention_bias.weight", (cfg["rel_buckets"], H)))
+            out += [(p + "grep_linear.weight", (cfg["gate_dim"], dh)), (p + "grep_linear.bias", (cfg["gate_dim"],)),
+                    (p + "grep_a", (1, H, 1, 1))]
+    return out
+
+
+def wavlm_rel_bucket(d: int, cfg=WAVLM_BASE) -> int:
+    """Bucket of the relative position d = key - query (bidirectional: d > 0, the key after
+    the query, takes the upper half).  Constant for |d| >= 778."""
+    import math
+    n = cfg["rel_buckets"] // 2
+    exact = n // 2
+    r = abs(d)
+    b = n if d > 0 else 0
+    if r < exact:
+        return b + r
+    return b + min(n - 1, int(exact + math.log(r / exact) / math.log(cfg["rel_max_distance"] / exact) * (n - exact)))
+
+
+def wavlm_gflop_per_utt(num_samples: int, cfg=WAVLM_BASE) -> float:
+    """hubert_gflop_per_utt plus the gate (two 64-long dot products per frame and head) and one
+    multiply-add per attention score."""
+    t = hubert_num_frames(num_samples, cfg)
+    extra = cfg["layers"] * (2 * t * cfg["hidden"] + t * t * cfg["heads"])
+    return hubert_gflop_per_utt(num_samples, cfg) + 2.0 * extra / 1e9

@@ -16,8 +16,8 @@ Semantics (bin/extract.py:33-120, dataset/dataset.py:136-247):
     frame_length, frame_shift; dither forced to 0, extract.py:66-67) at
     `resample_rate`, then apply_cmvn as `dataset_args.cmvn` / `cmvn_args`
     say (extract.py:104-106; norm_mean fused into the fbank launch, norm_var
-    a wsp_cmvn pass); or, with `dataset_args.frontend: s3prl` (hubert_base),
-    the HuBERT front end on [-1, 1] audio (extract.py:100-102) + CMVN, then
+    a wsp_cmvn pass); or, with `dataset_args.frontend: s3prl` (hubert_base,
+    wavlm_base, wavlm_base_plus), the SSL front end on [-1, 1] audio (extract.py:100-102) + CMVN, then
     the backbone on its 768-dim frames;
   * `--data_type feat`: JSON lines {key, feat, spk} whose `feat` is a
     kaldiio.load_mat specifier (processor.parse_feat, processor.py:171-196;

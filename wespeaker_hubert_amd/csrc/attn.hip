@@ -15,6 +15,14 @@
 // whole K / V once; the previous kernel (hubert.hip mha_kernel) streamed 32-key
 // chunks through a register / LDS ring with a barrier and an exposed global
 // load per chunk.
+//
+// WavLM (kBias instantiations): score(i, j) += gate[i][head] * table[head][j - i], the gated
+// bucketed relative-position bias.  The head's table (1557 floats over d in [-778, 778], the
+// range outside which the bucket is constant) sits in LDS behind the K / V planes; a lane's 16
+// scores of a chunk read table[d0 + {0..3, 8..11, 16..19, 24..27}] with d0 = key0 + 4 hh - query:
+// consecutive lanes (queries) read consecutive dwords downwards, the two half-waves overlap in all
+// but 4 of them (same address: broadcast), so the reads are bank-conflict-free.  The plain
+// instantiations compile to the code they had before the bias existed.
 #include "attn.h"
 #include "gemm_common.h"
 
@@ -58,8 +66,11 @@ __device__ __forceinline__ f32x16 mma3(const bf16x8& ah, const bf16x8& al, const
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
 }
 
+template <bool kBias>
 __global__ __launch_bounds__(512, 2) void attn_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ out,
-                                                      int ldo, int T_, int D, float scale, const int* __restrict__ seg) {
+                                                      int ldo, int T_, int D, float scale, const int* __restrict__ seg,
+                                                      const float* __restrict__ btab,
+                                                      const float* __restrict__ gate) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* kh_s = smem;
   unsigned char* kl_s = smem + kKPlane;
@@ -75,6 +86,16 @@ __global__ __launch_bounds__(512, 2) void attn_kernel(const float* __restrict__ 
   const float* base = qkv + rbase * ldq;
   const int q = q0 + wave * 32 + r;
   const bool wave_live = q0 + wave * 32 < T;  // wave-uniform
+
+  // bias table of this head behind the K / V planes (visible after the first staging barrier)
+  // and this lane's gate
+  const float* tb_s = reinterpret_cast<const float*>(smem + kLds);
+  float g = 0.f;
+  if constexpr (kBias) {
+    float* tw = reinterpret_cast<float*>(smem + kLds);
+    for (int i = tid; i < kAttnRelStride; i += 512) tw[i] = i < kAttnRelN ? btab[head * kAttnRelStride + i] : 0.f;
+    g = gate[(rbase + min(q, T - 1)) * gridDim.y + head];
+  }
 
   // Q^T fragments (B operand of S^T = K Q^T): lane = query r, d = 16 s + 8 hh + e;
   // pre-scaled by 1/sqrt(dh) = 1/8 (exact in binary)
@@ -146,6 +167,12 @@ __global__ __launch_bounds__(512, 2) void attn_kernel(const float* __restrict__ 
         const int ka = k_addr(key, 2 * s + hh);
         st = mma3(*reinterpret_cast<const bf16x8*>(kh_s + ka), *reinterpret_cast<const bf16x8*>(kl_s + ka), qh[s],
                   ql[s], st);
+      }
+      if constexpr (kBias) {  // positions past the table's ends share its end values
+        const int d0 = k0 + c * 32 + 4 * hh - min(q, T - 1) + kAttnRelMax;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          st[e] = fmaf(g, tb_s[min(max(d0 + (e & 3) + 8 * (e >> 2), 0), kAttnRelN - 1)], st[e]);
       }
       // online softmax over the keys of this lane's query column
       float cmax = -FLT_MAX;
@@ -222,13 +249,20 @@ constexpr int kVPlaneH = kDh * kVRowH;              // 16.5 KB per V^T plane
 constexpr int kBufH = 2 * kKPlaneH + 2 * kVPlaneH;  // one staged half
 constexpr int kLdsPipe = 2 * kBufH;                 // two buffers: 130 KB
 constexpr int kPerH = kKH * (kDh / 4) / 512;        // float4 pieces of K (and of V) per thread and half
+// kBias: two bias tables (the current item's head and the next one's) behind the K / V buffers,
+// 130 KB + 2 x 6240 B = 142.2 KB of the 160 KB
+constexpr int kLdsPipeBias = kLdsPipe + 2 * kAttnRelStride * 4;
+constexpr int kTabPer = (kAttnRelStride + 511) / 512;  // table floats per thread
 
 __device__ __forceinline__ int k_addr_h(int key, int chunk) { return key * 128 + ((chunk ^ ((key >> 1) & 7)) << 4); }
 
+template <bool kBias>
 __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restrict__ qkv, int ldq,
                                                            float* __restrict__ out, int ldo, int T_, int D, int H,
                                                            int nqb, int nitems, float scale,
-                                                           const int* __restrict__ seg) {
+                                                           const int* __restrict__ seg,
+                                                           const float* __restrict__ btab,
+                                                           const float* __restrict__ gate) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hh = lane >> 5;
 
@@ -305,9 +339,37 @@ __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restri
   f32x16 o[2];
   float m = -FLT_MAX, l = 0.f;
   int buf = 0;
+  // kBias: the item's head table (x log2(e): the scores are in the log2 domain) goes into one of
+  // two LDS tables at the item's first half, with the same barrier as that half's K / V.  The other
+  // table's last readers (the previous item's last half) are one barrier behind, like the other
+  // K / V buffer's.  g: this lane's gate, qc: its query clamped into the utterance
+  float* tab_s = reinterpret_cast<float*>(smem + kLdsPipe);
+  int tpar = 1, qc = 0;
+  float g = 0.f;
   while (true) {
     unsigned char* cur = smem + buf * kBufH;
+    float tv[kTabPer] = {};
+    if constexpr (kBias) {
+      if (hf == 0) {  // block-uniform; issued behind the K / V loads, whose conversion does not wait for these
+        tpar ^= 1;
+        const float* th = btab + ((it / nqb) % H) * kAttnRelStride;
+#pragma unroll
+        for (int i = 0; i < kTabPer; ++i) {
+          const int idx = tid + 512 * i;
+          tv[i] = idx < kAttnRelN ? th[idx] * 1.4426950408889634f : 0.f;
+        }
+      }
+    }
     write_half(cur);
+    if constexpr (kBias) {
+      if (hf == 0) {
+#pragma unroll
+        for (int i = 0; i < kTabPer; ++i) {
+          const int idx = tid + 512 * i;
+          if (idx < kAttnRelStride) tab_s[tpar * kAttnRelStride + idx] = tv[i];
+        }
+      }
+    }
     __syncthreads();  // the half is in LDS; the other buffer's readers are one barrier behind
     const int T = item_T(it);
     const int head = (it / nqb) % H;
@@ -331,6 +393,11 @@ __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restri
         for (int e = 0; e < 16; ++e) o[t][e] = 0.f;
       m = -FLT_MAX;
       l = 0.f;
+      if constexpr (kBias) {
+        qc = min(q, T - 1);
+        const size_t row0 = seg ? (size_t)seg[it / (H * nqb)] : (size_t)(it / (H * nqb)) * T_;
+        g = gate[(row0 + qc) * H + head];
+      }
     }
     int nit = it, nhf = hf;
     next(nit, nhf);
@@ -343,6 +410,10 @@ __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restri
       const unsigned char* vh_s = cur + 2 * kKPlaneH;
       const unsigned char* vl_s = vh_s + kVPlaneH;
       const int nch = (nk + 31) / 32;
+      // kBias: with every key of the item's (zero-padded) halves and every query within 778 of each
+      // other the table index needs no clamp (item-uniform; utterances up to 768 frames)
+      const float* tb = tab_s + tpar * kAttnRelStride;
+      const bool noclamp = (T + kKH - 1) / kKH * kKH <= kAttnRelMax + 1;
       for (int c = 0; c < nch; ++c) {
         f32x16 st;
 #pragma unroll
@@ -353,6 +424,17 @@ __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restri
           const int ka = k_addr_h(key, 2 * s + hh);
           st = mma3(*reinterpret_cast<const bf16x8*>(kh_s + ka), *reinterpret_cast<const bf16x8*>(kl_s + ka), qh[s],
                     ql[s], st);
+        }
+        if constexpr (kBias) {
+          const int d0 = k0 + c * 32 + 4 * hh - qc + kAttnRelMax;
+          if (noclamp) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) st[e] = fmaf(g, tb[d0 + (e & 3) + 8 * (e >> 2)], st[e]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+              st[e] = fmaf(g, tb[min(max(d0 + (e & 3) + 8 * (e >> 2), 0), kAttnRelN - 1)], st[e]);
+          }
         }
         // online softmax in the log2 domain with a lazy maximum (r5): the running max m moves
         // only when a score exceeds it by more than 8 (p <= 2^8 then; l <= 2^8 x keys), so the
@@ -430,23 +512,66 @@ __global__ __launch_bounds__(512, 2) void attn_pipe_kernel(const float* __restri
   }
 }
 
+// WavLM gate: 16 lanes per (row, head), one float4 of the head's 64 inputs each; the 8 outputs of
+// grep_linear enter only as two sums of 4, so the host sums its rows and two dot products remain.
+__global__ __launch_bounds__(256) void attn_gate_kernel(const float* __restrict__ x, int ldx, int n, int H,
+                                                        const float* __restrict__ w, float* __restrict__ gate) {
+  const int sub = threadIdx.x & 15;
+  const int idx = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int ic = min(idx, n - 1);
+  const int row = ic / H, head = ic % H;
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)row * ldx + head * kDh + 4 * sub);
+  const f32x4 wa = *reinterpret_cast<const f32x4*>(w + 4 * sub);
+  const f32x4 wb = *reinterpret_cast<const f32x4*>(w + kDh + 4 * sub);
+  float a = xv[0] * wa[0] + xv[1] * wa[1] + xv[2] * wa[2] + xv[3] * wa[3];
+  float b = xv[0] * wb[0] + xv[1] * wb[1] + xv[2] * wb[2] + xv[3] * wb[3];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  if (sub == 0 && idx < n) {
+    const float ga = 1.f / (1.f + expf(-(a + w[2 * kDh])));
+    const float gb = 1.f / (1.f + expf(-(b + w[2 * kDh + 1])));
+    gate[idx] = ga * (gb * w[2 * kDh + 2 + head] - 1.f) + 2.f;
+  }
+}
+
 }  // namespace
 
 void launch_attn(const float* qkv, int ldq, float* out, int ldo, int B, int T, int H, int dh, hipStream_t s,
-                 const int* seg, int pipe) {
+                 const int* seg, int pipe, const AttnBias* bias) {
   WSP_CHECK(dh == kDh, "attn: head dim must be 64");
   WSP_CHECK(B > 0 && T > 0 && H > 0 && ldq >= 3 * H * dh && ldq % 4 == 0 && ldo % 4 == 0, "attn: bad shape");
+  WSP_CHECK(!bias || (bias->table && bias->gate), "attn: bias needs its table and gate");
+  const float* nul = nullptr;
   if (pipe) {
     const int ncu = device_cu_count();
     const int nqb = (T + kQB - 1) / kQB;  // segmented: T = longest utterance
     const int nitems = B * H * nqb;
-    hipLaunchKernelGGL(attn_pipe_kernel, dim3(std::min(nitems, ncu)), dim3(512), kLdsPipe, s, qkv, ldq, out, ldo, T,
-                       H * dh, H, nqb, nitems, 1.f / sqrtf((float)dh), seg);
+    if (bias)
+      hipLaunchKernelGGL(attn_pipe_kernel<true>, dim3(std::min(nitems, ncu)), dim3(512), kLdsPipeBias, s, qkv, ldq, out,
+                         ldo, T, H * dh, H, nqb, nitems, 1.f / sqrtf((float)dh), seg, bias->table, bias->gate);
+    else
+      hipLaunchKernelGGL(attn_pipe_kernel<false>, dim3(std::min(nitems, ncu)), dim3(512), kLdsPipe, s, qkv, ldq, out,
+                         ldo, T, H * dh, H, nqb, nitems, 1.f / sqrtf((float)dh), seg, nul, nul);
   } else {
     const dim3 grid((T + kQB - 1) / kQB, H, B);  // segmented: T = longest utterance
-    hipLaunchKernelGGL(attn_kernel, grid, dim3(512), kLds, s, qkv, ldq, out, ldo, T, H * dh, 1.f / sqrtf((float)dh),
-                       seg);
+    if (bias)
+      hipLaunchKernelGGL(attn_kernel<true>, grid, dim3(512), kLds + kAttnRelStride * 4, s, qkv, ldq, out, ldo, T,
+                         H * dh, 1.f / sqrtf((float)dh), seg, bias->table, bias->gate);
+    else
+      hipLaunchKernelGGL(attn_kernel<false>, grid, dim3(512), kLds, s, qkv, ldq, out, ldo, T, H * dh,
+                         1.f / sqrtf((float)dh), seg, nul, nul);
   }
+  WSP_HIP(hipGetLastError());
+}
+
+void launch_attn_gate(const float* x, int ldx, int rows, int H, const float* w, float* gate, hipStream_t s) {
+  WSP_CHECK(rows > 0 && H > 0 && ldx >= H * kDh && ldx % 4 == 0, "attn_gate: bad shape");
+  const long long n = (long long)rows * H;
+  WSP_CHECK(n < (1LL << 31), "attn_gate: too many rows");
+  hipLaunchKernelGGL(attn_gate_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, x, ldx, (int)n, H, w, gate);
   WSP_HIP(hipGetLastError());
 }
 

@@ -1,4 +1,6 @@
-// HuBERT-base SSL front end runtime (arch "HuBERT_base").
+// HuBERT-base SSL front end runtime (arch "HuBERT_base"), and WavLM Base / Base+
+// (arch "WavLM_base": the same network with a gated relative-position bias in
+// every attention, attn.hip; s3prl `wavlm_base` / `wavlm_base_plus`).
 //
 // Replaces S3prlFrontend.forward (wespeaker/frontend/s3prl.py:80-93) with the
 // s3prl `hubert` upstream (third party, restated in oracle/hubert_ref.py):
@@ -26,6 +28,7 @@ constexpr int kConvK[7] = {10, 3, 3, 3, 3, 2, 2};
 constexpr int kConvS[7] = {5, 2, 2, 2, 2, 2, 2};
 constexpr int kDownsample = 320;
 constexpr int kMinSamples = 800;  // s3prl MIN_SECOND (0.05 s) * 16 kHz
+constexpr int kRelBuckets = 320, kRelMaxDist = 800;  // WavLM relative_attention_bias
 const char* const kPre = "frontend.upstream.upstream.model.";
 
 std::string hp(const std::string& n) { return std::string(kPre) + n; }
@@ -64,8 +67,26 @@ void Model::Impl::build_hubert_params() {
     add(hp(p + "fc2.bias"), {kHidden});
     add(hp(p + "final_layer_norm.weight"), {kHidden});
     add(hp(p + "final_layer_norm.bias"), {kHidden});
+    if (wavlm) {
+      // gated relative-position bias: the bucket embedding lives in layer 0 and serves every layer
+      if (l == 0) add(hp(p + "self_attn.relative_attention_bias.weight"), {kRelBuckets, kHeads});
+      add(hp(p + "self_attn.grep_linear.weight"), {8, kHidden / kHeads});
+      add(hp(p + "self_attn.grep_linear.bias"), {8});
+      add(hp(p + "self_attn.grep_a"), {1, kHeads, 1, 1});
+    }
   }
   add("frontend.featurizer.weights", {kLayers + 1});
+}
+
+// WavLM relative-position bucket of d = key - query (num_buckets 320, max_distance 800,
+// bidirectional): 160 per sign (d > 0: +160), |d| < 80 exact, then 80 log-spaced up to 159.
+static int wavlm_rel_bucket(int d) {
+  const int n = kRelBuckets / 2, exact = n / 2;
+  const int r = std::abs(d);
+  const int b = d > 0 ? n : 0;
+  if (r < exact) return b + r;
+  const int big = exact + (int)(std::log((double)r / exact) / std::log((double)kRelMaxDist / exact) * (n - exact));
+  return b + std::min(big, n - 1);
 }
 
 void Model::Impl::finalize_hubert() {
@@ -152,6 +173,38 @@ void Model::Impl::finalize_hubert() {
     }
     L.ln2_g = dev.upload(P(hp(p + "final_layer_norm.weight")));
     L.ln2_b = dev.upload(P(hp(p + "final_layer_norm.bias")));
+    if (wavlm) {
+      // the gate reads grep_linear's 8 outputs only as sum(p[0:4]) and sum(p[4:8]): two dot products
+      // with the summed rows (f64)
+      const auto& gw = P(hp(p + "self_attn.grep_linear.weight"));
+      const auto& gb = P(hp(p + "self_attn.grep_linear.bias"));
+      const auto& ga = P(hp(p + "self_attn.grep_a"));
+      const int dh = kHidden / kHeads;
+      std::vector<float> pk(2 * dh + 2 + kHeads);
+      for (int half = 0; half < 2; ++half) {
+        double bs = 0.0;
+        for (int j = 0; j < 4; ++j) bs += gb[4 * half + j];
+        pk[2 * dh + half] = (float)bs;
+        for (int c = 0; c < dh; ++c) {
+          double ws = 0.0;
+          for (int j = 0; j < 4; ++j) ws += gw[(size_t)(4 * half + j) * dh + c];
+          pk[half * dh + c] = (float)ws;
+        }
+      }
+      for (int h = 0; h < kHeads; ++h) pk[2 * dh + 2 + h] = ga[h];
+      L.gate_w = dev.upload(pk);
+    }
+  }
+  if (wavlm) {
+    // bias[h][d + 778] = weight[bucket(d)][h]; the bucket is constant past either end
+    static_assert(kAttnRelMax == 778 && kRelBuckets == 320 && kRelMaxDist == 800, "table range follows the buckets");
+    const auto& rw = P(hp("encoder.layers.0.self_attn.relative_attention_bias.weight"));
+    std::vector<float> tab((size_t)kHeads * kAttnRelStride, 0.f);
+    for (int d = -kAttnRelMax; d <= kAttnRelMax; ++d) {
+      const int bk = wavlm_rel_bucket(d);
+      for (int h = 0; h < kHeads; ++h) tab[(size_t)h * kAttnRelStride + d + kAttnRelMax] = rw[(size_t)bk * kHeads + h];
+    }
+    h_rel_tab = dev.upload(tab);
   }
   // Featurizer weights: softmax over the 13 hidden states (s3prl Featurizer,
   // normalize=False), or a one-hot pick for `layer != -1` (s3prl.py:84-87).
@@ -253,9 +306,10 @@ size_t Model::Impl::hubert_ws_floats(const HubertPlan& pl, size_t* offs) const {
                           M * kHidden,        M * kFfn,                                                // ao, ffn / pos
                           pl.offs.size(),                                                              // int32 offsets
                           M * (kHidden / 128) * 2,                                                     // LN partials
-                          pl.tail_batch ? pl.M3 * kConvDim : 0};                                       // level-3 rows
+                          pl.tail_batch ? pl.M3 * kConvDim : 0,                                        // level-3 rows
+                          wavlm ? M * kHeads : 0};                                                     // WavLM gate
   size_t o = 0;
-  for (int i = 0; i < 11; ++i) {
+  for (int i = 0; i < 12; ++i) {
     if (offs) offs[i] = o;
     o += (sizes[i] + 63) / 64 * 64;
   }
@@ -264,7 +318,7 @@ size_t Model::Impl::hubert_ws_floats(const HubertPlan& pl, size_t* offs) const {
 
 void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws,
                                  hipStream_t s) {
-  size_t off[11];
+  size_t off[12];
   hubert_ws_floats(pl, off);
   float* cnnA = ws + off[0];
   float* cnnB = ws + off[1];
@@ -288,6 +342,7 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
   const int* gseg4 = dseg + 3 * (B + 1);
   const int* gseg5 = dseg + 4 * (B + 1);
   float* cnn3 = ws + off[10];       // tail_batch: [M3][512] level-3 rows of the whole batch
+  float* gate = ws + off[11];       // WavLM: [M][12] gate of the layer in flight
 
   auto conv = [&](const char* tag, const ConvW& cw, const float* a, int lda, float* out, int ldo, int rows, int Ti,
                   int stride, int pad, int act, const float* res, bool bias, const int* oseg, const int* iseg, int nseg,
@@ -415,8 +470,13 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
   for (int l = 0; l < kLayers; ++l) {
     const HLayer& L = h_layers[l];
     conv("h_qkv", L.qkv, x, kHidden, qkv, 3 * kHidden, M, M, 1, 0, kActNone, nullptr, true, nullptr, nullptr, 0);
-    run("h_attn", 4.0 * B * kHeads * (double)pl.maxT6 * pl.maxT6 * (kHidden / kHeads), s,
-        [&] { launch_attn(qkv, 3 * kHidden, ao, kHidden, B, pl.maxT6, kHeads, kHidden / kHeads, s, seg6, attn_pipe); });
+    AttnBias ab{h_rel_tab, gate};
+    if (wavlm)  // the gate comes from the layer input x, not from q
+      run("h_gate", 4.0 * M * kHidden, s, [&] { launch_attn_gate(x, kHidden, M, kHeads, L.gate_w, gate, s); });
+    run("h_attn", 4.0 * B * kHeads * (double)pl.maxT6 * pl.maxT6 * (kHidden / kHeads), s, [&] {
+      launch_attn(qkv, 3 * kHidden, ao, kHidden, B, pl.maxT6, kHeads, kHidden / kHeads, s, seg6, attn_pipe,
+                  wavlm ? &ab : nullptr);
+    });
     if (fold) {
       // LN1 folded: out_proj emits x1's row statistics, fc1 runs on x1 with gamma1 / beta1 in its
       // weights, fc2 normalises its residual x1 on the fly (in place: each element is read by the

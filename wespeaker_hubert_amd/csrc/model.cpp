@@ -85,12 +85,14 @@ void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool em
     const int nb34[4] = {3, 4, 6, 3}, nb100[4] = {6, 16, 24, 3};
     for (int i = 0; i < 4; ++i) m.nblocks[i] = arch == "SimAM_ResNet34_ASP" ? nb34[i] : nb100[i];
     m.build_simam_params();
-  } else if (arch == "HuBERT_base") {
-    // s3prl HuBERT-base upstream + Featurizer (frontend/s3prl.py); input is
-    // the waveform, output 768-dim frames (S3prlFrontend.output_size()).
-    WSP_CHECK(embed_dim == 768, "HuBERT_base output size is 768");
+  } else if (arch == "HuBERT_base" || arch == "WavLM_base") {
+    // s3prl HuBERT-base / WavLM Base(+) upstream + Featurizer (frontend/s3prl.py); input is
+    // the waveform, output 768-dim frames (S3prlFrontend.output_size()).  WavLM_base is the
+    // HuBERT-base network with a gated relative-position bias in every attention.
+    WSP_CHECK(embed_dim == 768, arch + " output size is 768");
     m.ecapa = false;
     m.hubert = true;
+    m.wavlm = arch == "WavLM_base";
     m.feat_dim = 1;
     m.x3_variant = 7;  // every GEMM whose operands family 7 takes (r4), the rest on 6
     m.streams = 2;  // HuBERT + ECAPA C4 chain +2.6 %

@@ -223,7 +223,11 @@ struct Model::Impl {
     // and W beta1 into the bias; fc1_cs[n] = sum_c W'[n][c] (of the bf16 hi + lo images)
     ConvW fc1f;
     float* fc1_cs = nullptr;
+    float* gate_w = nullptr;  // WavLM: [wa (64) | wb (64) | ba | bb | grep_a (12)] (attn.h launch_attn_gate)
   };
+  // WavLM Base / Base+ (arch "WavLM_base"): HuBERT-base plus the gated relative-position bias
+  bool wavlm = false;
+  float* h_rel_tab = nullptr;  // [12][kAttnRelStride] bias per head over d = key - query in [-778, 778]
   std::vector<HLayer> h_layers;
   std::vector<float> h_fw;  // featurizer weight per hidden state
   int h_layer_sel = -1;     // s3prl `layer` (-1: softmax-weighted sum of all 13)

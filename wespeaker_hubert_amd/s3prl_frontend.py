@@ -1,4 +1,4 @@
-"""HuBERT-base SSL front end on the HIP path — mirror of
+"""HuBERT-base / WavLM Base(+) SSL front end on the HIP path — mirror of
 `wespeaker.frontend.s3prl.S3prlFrontend` (wespeaker/frontend/s3prl.py:23-93).
 
 Same constructor arguments, `output_size()` and `forward(wavs, wavs_len) ->
@@ -8,12 +8,16 @@ Weights arrive under the reference checkpoint's names
 (`frontend.upstream.upstream.model.<fairseq name>`, `frontend.featurizer.weights`;
 the module-local form without the `frontend.` prefix is accepted too).
 
-Implemented: upstream name `hubert_base` (alias `hubert`), normalize=False,
+Implemented: upstream names `hubert_base` (alias `hubert`), `wavlm_base` and
+`wavlm_base_plus` (one architecture: HuBERT-base with a gated relative-position
+bias in every attention; extra parameters in arch.wavlm_params()), normalize=False,
 equal-length batches (what bin/extract.py:100-102 feeds), ragged batches of whole
 utterances (`extract_segments`: every utterance computed as if alone — GroupNorm,
 pos-conv padding, attention and featurizer all per utterance), multilayer_feature /
 layer selection.  s3prl itself is absent offline, so its glue (length match,
 Featurizer) is restated — see oracle/hubert_ref.py for the pinning status.
+Not implemented: `wavlm_large` (24 pre-LN layers of width 1024, LayerNorm after
+every CNN conv, normalize=True).
 """
 from __future__ import annotations
 
@@ -24,14 +28,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arch import HUBERT_BASE, hubert_params
+from .arch import HUBERT_BASE, WAVLM_UPSTREAMS, hubert_params, wavlm_params
 from .speaker_model import _HipHandle
 
-SUPPORTED_UPSTREAMS = ("hubert_base", "hubert")
+SUPPORTED_UPSTREAMS = ("hubert_base", "hubert") + WAVLM_UPSTREAMS
 
 
 class S3prlFrontend(_HipHandle):
-    """Speech pretrained representation front end (HuBERT-base on gfx950)."""
+    """Speech pretrained representation front end (HuBERT-base, WavLM Base / Base+ on gfx950)."""
 
     _ignored_prefixes = (
         # fairseq HubertModel members the extraction forward never reads
@@ -45,10 +49,15 @@ class S3prlFrontend(_HipHandle):
                  sample_rate: int = 16000):
         super().__init__()
         name = (upstream_args or {}).get("name", None)
+        if name == "wavlm_large":
+            raise NotImplementedError(
+                "s3prl upstream 'wavlm_large' is not implemented: it has 24 pre-LN layers of width 1024, LayerNorm "
+                f"after every CNN conv and normalize=True; supported upstreams are {SUPPORTED_UPSTREAMS}")
         if name not in SUPPORTED_UPSTREAMS:
             raise NotImplementedError(f"s3prl upstream {name!r}: only {SUPPORTED_UPSTREAMS} run on the MI355X path")
         if (upstream_args or {}).get("normalize", False):
-            raise NotImplementedError("upstream normalize=True is not implemented (HuBERT-base uses False)")
+            raise NotImplementedError("upstream normalize=True is not implemented (HuBERT-base and WavLM Base / "
+                                      "Base+ use False)")
         if layer != -1 and multilayer_feature:
             raise AssertionError("multilayer_feature must be False if layer is specified")  # s3prl.py:60-61
         self.multilayer_feature = multilayer_feature
@@ -59,7 +68,9 @@ class S3prlFrontend(_HipHandle):
         self.downsample_rate = 320
         # s3prl.py:69: featurizer.downsample_rate == sample_rate * frame_shift // 1000
         assert self.downsample_rate == sample_rate * frame_shift // 1000
-        self._layout = hubert_params()
+        self.upstream_name = name
+        self._arch = "WavLM_base" if name in WAVLM_UPSTREAMS else "HuBERT_base"
+        self._layout = wavlm_params() if name in WAVLM_UPSTREAMS else hubert_params()
         self._pre_finalize = ("layer",)
         if layer != -1:
             self._options["layer"] = int(layer)
@@ -69,7 +80,7 @@ class S3prlFrontend(_HipHandle):
             self._options["layer"] = -1
 
     def _create_args(self):
-        return "HuBERT_base", 1, HUBERT_BASE["hidden"], False, False
+        return self._arch, 1, HUBERT_BASE["hidden"], False, False
 
     def _canonical(self, key: str) -> str:
         return key if key.startswith("frontend.") else "frontend." + key

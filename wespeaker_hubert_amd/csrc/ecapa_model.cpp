@@ -1,0 +1,286 @@
+// ECAPA-TDNN: parameter table, weight folding / packing, workspace and forward schedule.
+//
+// Forward = wespeaker/models/ecapa_tdnn.py:208-234, channels-last:
+//   layer1  Conv1dReluBn(F->C, k5)                        -> x1   [M][C]
+//   layerL  SE_Res2Block(dil L):  c1 (1x1) -> h1
+//           Res2 chain i=0..6: conv_k3(h1_i (+ h2_{i-1})) -> h2_i  (7 GEMMs)
+//           c3 (1x1) over cat(h2_0..6, h1_7)             -> h3   (no copy)
+//           SE: frame mean -> FC relu -> FC sigmoid -> x_{L} + h3 * g
+//   conv    1x1 over cat(x2, x3, x4) (no copy), ReLU      -> xp   [M][1536]
+//   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
+//           -> online-softmax attentive mean/std          -> [B][3072]
+//   head    BN(3072) + Linear (+ bn2) folded into one GEMV -> embed [B][D]
+#include "model_impl.h"
+
+namespace wsp {
+
+void Model::Impl::build_ecapa_params() {
+  const int64_t C = this->C, w = C / 8;
+  add("layer1.conv.weight", {C, feat_dim, 5});
+  add("layer1.conv.bias", {C});
+  add_bn("layer1.bn", C);
+  for (int li = 2; li <= 4; ++li) {
+    const std::string p = "layer" + std::to_string(li) + ".se_res2block";
+    add(p + ".0.conv.weight", {C, C, 1});
+    add(p + ".0.conv.bias", {C});
+    add_bn(p + ".0.bn", C);
+    for (int i = 0; i < 7; ++i) {
+      add(p + ".1.convs." + std::to_string(i) + ".weight", {w, w, 3});
+      add(p + ".1.convs." + std::to_string(i) + ".bias", {w});
+    }
+    for (int i = 0; i < 7; ++i) add_bn(p + ".1.bns." + std::to_string(i), w);
+    add(p + ".2.conv.weight", {C, C, 1});
+    add(p + ".2.conv.bias", {C});
+    add_bn(p + ".2.bn", C);
+    add(p + ".3.linear1.weight", {128, C});
+    add(p + ".3.linear1.bias", {128});
+    add(p + ".3.linear2.weight", {C, 128});
+    add(p + ".3.linear2.bias", {C});
+  }
+  add("conv.weight", {1536, 3 * C, 1});
+  add("conv.bias", {1536});
+  add("pool.linear1.weight", {128, glob ? 4608 : 1536, 1});
+  add("pool.linear1.bias", {128});
+  add("pool.linear2.weight", {1536, 128, 1});
+  add("pool.linear2.bias", {1536});
+  add_bn("bn", 3072);
+  add("linear.weight", {embed_dim, 3072});
+  add("linear.bias", {embed_dim});
+  if (emb_bn) add_bn("bn2", embed_dim);
+}
+
+// Res2Net chain weights for res2_chain.hip (pack::frag_res2); conv bias and eval-BN affine per
+// step [7][w].
+void Model::Impl::pack_res2(Block& b, const std::string& p, int w) {
+  const std::vector<float>* W[7];
+  std::vector<float> bias((size_t)7 * w), sc((size_t)7 * w), sh((size_t)7 * w);
+  for (int i = 0; i < 7; ++i) {
+    const std::string ci = p + ".1.convs." + std::to_string(i);
+    W[i] = &P(ci + ".weight");
+    const auto& bb = P(ci + ".bias");
+    std::vector<double> s, t;
+    bn_affine(p + ".1.bns." + std::to_string(i), s, t);
+    for (int n = 0; n < w; ++n) {
+      bias[(size_t)i * w + n] = bb[n];
+      sc[(size_t)i * w + n] = (float)s[n];
+      sh[(size_t)i * w + n] = (float)t[n];
+    }
+  }
+  b.r2w = dev.upload_u16(pack::frag_res2(W, w));
+  b.r2b = dev.upload(bias);
+  b.r2s = dev.upload(sc);
+  b.r2t = dev.upload(sh);
+}
+
+void Model::Impl::finalize_ecapa() {
+  const int w = C / 8;
+  layer1 = pack_conv(P("layer1.conv.weight"), C, feat_dim, 5, P("layer1.conv.bias").data(), "layer1.bn");
+  for (int li = 0; li < 3; ++li) {
+    const std::string p = "layer" + std::to_string(li + 2) + ".se_res2block";
+    Block& b = blk[li];
+    b.c1 = pack_conv(P(p + ".0.conv.weight"), C, C, 1, P(p + ".0.conv.bias").data(), p + ".0.bn");
+    for (int i = 0; i < 7; ++i) {
+      const std::string ci = p + ".1.convs." + std::to_string(i);
+      b.res2[i] = pack_conv(P(ci + ".weight"), w, w, 3, P(ci + ".bias").data(), p + ".1.bns." + std::to_string(i));
+    }
+    if (res2_chain_supported(w, li + 2)) pack_res2(b, p, w);
+    b.c3 = pack_conv(P(p + ".2.conv.weight"), C, C, 1, P(p + ".2.conv.bias").data(), p + ".2.bn");
+    b.se1 = pack_lin(P(p + ".3.linear1.weight").data(), 128, C, C, P(p + ".3.linear1.bias").data());
+    b.se2 = pack_lin(P(p + ".3.linear2.weight").data(), C, 128, 128, P(p + ".3.linear2.bias").data());
+  }
+  conv = pack_conv(P("conv.weight"), 1536, 3 * C, 1, P("conv.bias").data(), "");
+  {
+    std::vector<float> wg = P("conv.weight");  // [1536][3C]
+    for (int n = 0; n < 1536; ++n)
+      for (int c = 0; c < C; ++c) {
+        float* r = wg.data() + (size_t)n * 3 * C;
+        r[C + c] = (float)((double)r[C + c] + (double)r[2 * C + c]);
+      }
+    conv_g = pack_conv(wg, 1536, 3 * C, 1, P("conv.bias").data(), "");
+  }
+  const auto& l1 = P("pool.linear1.weight");
+  const int l1k = glob ? 4608 : 1536;
+  {
+    std::vector<float> wx((size_t)128 * 1536);
+    for (int n = 0; n < 128; ++n)
+      for (int k = 0; k < 1536; ++k) wx[(size_t)n * 1536 + k] = l1[(size_t)n * l1k + k];
+    pool1 = pack_conv(wx, 128, 1536, 1, P("pool.linear1.bias").data(), "");
+    if (glob) {
+      // columns 1536..4607 multiply the (constant over T) mean/std context:
+      // folded into a per-utterance bias computed by small_linear.
+      pool1_ctx = pack_lin(l1.data() + 1536, 128, 3072, l1k, P("pool.linear1.bias").data());
+    }
+  }
+  pool2 = pack_conv(P("pool.linear2.weight"), 1536, 128, 1, P("pool.linear2.bias").data(), "");
+  pool2_frag = pack_frag(P("pool.linear2.weight"), 1536, 128);
+  // head: y = Linear(BN(p)) [-> bn2] folded to y = W' p + b'
+  {
+    std::vector<double> s, t;
+    bn_affine("bn", s, t);
+    const auto& W = P("linear.weight");
+    const auto& bb = P("linear.bias");
+    const int D = embed_dim;
+    std::vector<double> s2(D, 1.0), t2(D, 0.0);
+    if (emb_bn) bn_affine("bn2", s2, t2);
+    std::vector<float> wf((size_t)D * 3072), bf(D);
+    for (int n = 0; n < D; ++n) {
+      double acc = bb[n];
+      for (int k = 0; k < 3072; ++k) {
+        const double wv = W[(size_t)n * 3072 + k];
+        wf[(size_t)n * 3072 + k] = (float)(s2[n] * wv * s[k]);
+        acc += wv * t[k];
+      }
+      bf[n] = (float)(s2[n] * acc + t2[n]);
+    }
+    head = pack_lin(wf.data(), D, 3072, 3072, bf.data());
+  }
+}
+
+// utterances per ECAPA forward chunk (uniform batches): the widest activation operand is the
+// [M][1536] ASTP input / logits; larger batches run as consecutive chunks over one chunk-sized
+// workspace (as resnet_chunk)
+int Model::Impl::ecapa_chunk(int B, int T) const {
+  return chunk_for(B, (size_t)T * std::max(C, 1536) * sizeof(float));
+}
+
+namespace {
+// M = frame rows of the batch (B * T, or the segment total)
+struct EcapaWs {
+  float *x[5], *h1, *h2, *h3, *gmean, *ghid, *gate, *xp, *att, *logit, *gstats, *rowb, *pooled;
+  double* sesum;  // SE column-sum partials (f64)
+  size_t floats;
+};
+EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base) {
+  WsCursor c{base};
+  EcapaWs w;
+  w.x[0] = nullptr;
+  for (int i = 1; i <= 4; ++i) w.x[i] = c.take(M * C);
+  w.h1 = c.take(M * C);
+  w.h2 = c.take(M * C);
+  w.h3 = c.take(M * C);
+  w.gmean = c.take(B * C);
+  w.ghid = c.take(B * 128);
+  w.gate = c.take(B * C);
+  w.xp = c.take(M * 1536);
+  w.att = c.take(M * 128);
+  w.logit = c.take(M * 1536);
+  w.gstats = c.take(B * 3072);
+  w.rowb = c.take(B * 128);
+  w.pooled = c.take(B * 3072);
+  w.sesum = reinterpret_cast<double*>(c.take(((M + 127) / 128) * 2 * C * 2));
+  w.floats = c.off;
+  return w;
+}
+}  // namespace
+
+size_t Model::Impl::ecapa_ws_floats(int B, size_t M) const { return ecapa_ws(C, B, M, nullptr).floats; }
+
+void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
+                                const int* seg, int M_seg) {
+  const int M = seg ? M_seg : B * T, w = C / 8;
+  const EcapaWs W = ecapa_ws(C, B, M, ws);
+  float* const* x = W.x;
+  float *h1 = W.h1, *h2 = W.h2, *h3 = W.h3, *xp = W.xp;
+  // SE squeeze fused into conv3's epilogue (per-utterance f64 column sums) on the
+  // bf16x3 path for uniform batches whose utterances span >= one block of rows
+  const int se_bm = precision == 1 ? conv_gemm_x3_block_rows(ConvGemmArgs{.N = C}, x3_variant) : 0;
+  const bool se_fused = precision == 1 && !seg && T >= se_bm;
+  // a GEMM whose three A slots (set by the caller) cat / add different [M][C] tensors
+  auto gemm3 = [&](const char* tag, ConvGemmArgs& g, const ConvW& cw, int dil, int pad, float* out, int ldo) {
+    g.lda[0] = g.lda[1] = g.lda[2] = C;
+    fill(g, cw, M, T, dil, pad, out, ldo, kActRelu, nullptr, true, seg, B);
+    run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch(g, cw, s); });
+  };
+
+  gemm("layer1", layer1, feats, feat_dim, x[1], C, M, T, 1, 2, kActRelu, s, seg, B);
+  for (int li = 0; li < 3; ++li) {
+    const Block& b = blk[li];
+    const int dil = li + 2;
+    const float* xin = x[li + 1];
+    gemm("conv1x1_CxC", b.c1, xin, C, h1, C, M, T, 1, 0, kActRelu, s, seg, B, nullptr, true, 1);
+    if (precision == 1 && res2_fused && b.r2w) {
+      // the whole chain in one launch (res2_chain.hip)
+      Res2Args r{};
+      r.x = h1;
+      r.out = h2;
+      r.ldx = r.ldo = C;
+      r.M = M;
+      r.T = T;
+      r.dil = dil;
+      r.variant = w == 128 ? res2_variant : std::min(res2_variant, 3);
+      r.rout = res2_chain_rout(dil, r.variant, M);
+      r.seg = seg;
+      r.nseg = B;
+      r.w = b.r2w;
+      r.bias = b.r2b;
+      r.scale = b.r2s;
+      r.shift = b.r2t;
+      run("res2_k3", 7 * 2.0 * M * w * 3 * w, s, [&] { launch_res2_chain(r, w, s); });
+    } else {
+      for (int i = 0; i < 7; ++i) {  // h1_0 alone, then h1_i + h2_{i-1}
+        ConvGemmArgs g{};
+        g.amode = i == 0 ? kACat : kAAdd;
+        if (i == 0) {
+          one_operand(g, h1, C, w);
+        } else {
+          g.a[0] = h1 + i * w;
+          g.a[1] = h2 + (i - 1) * w;
+          g.a[2] = h1;
+        }
+        gemm3("res2_k3", g, b.res2[i], dil, dil, h2 + i * w, C);
+      }
+    }
+    {
+      ConvGemmArgs g{};
+      g.amode = kACat;
+      g.a[0] = h2;
+      g.a[1] = h1 + 7 * w;
+      g.a[2] = h1;
+      g.cseg[1] = 7 * w;
+      g.cseg[2] = g.cseg[3] = C;
+      g.role = 1;
+      if (se_fused) g.colsum = W.sesum;
+      gemm3("conv1x1_CxC", g, b.c3, 1, 0, h3, C);
+    }
+    run("se", 0, s, [&] {
+      if (se_fused) launch_colsum_mean(W.sesum, se_bm, T, B, C, W.gmean, C, s);
+      else launch_frame_stats(h3, C, B, T, C, W.gmean, C, 0, 0, s, seg);
+      launch_small_linear({W.gmean, C, b.se1.wt, b.se1.bias, W.ghid, 128, B, C, 128, 1}, s);
+      launch_small_linear({W.ghid, 128, b.se2.wt, b.se2.bias, W.gate, C, B, 128, C, 3}, s);
+      // cat_gate: the last block stores only g4 * h3 (conv_cat adds out3 through its weights)
+      launch_residual_scale(cat_gate && li == 2 ? nullptr : xin, h3, W.gate, x[li + 2], B, T, C, s, seg, M);
+    });
+  }
+  {
+    ConvGemmArgs g{};
+    g.amode = kACat;
+    g.a[0] = x[2];
+    g.a[1] = x[3];
+    g.a[2] = x[4];
+    g.cseg[1] = C;
+    g.cseg[2] = 2 * C;
+    g.cseg[3] = 3 * C;
+    gemm3("conv_cat", g, cat_gate ? conv_g : conv, 1, 0, xp, 1536);
+  }
+  if (glob) {
+    run("glob_ctx", 0, s, [&] {
+      launch_frame_stats(xp, 1536, B, T, 1536, W.gstats, 3072, 1, 1536, s, seg);
+      launch_small_linear({W.gstats, 3072, pool1_ctx.wt, pool1_ctx.bias, W.rowb, 128, B, 3072, 128, 0}, s);
+    });
+  }
+  // GLOB: the context's per-utterance row bias carries pool.linear1's bias
+  gemm("pool_linear1", pool1, xp, 1536, W.att, 128, M, T, 1, 0, kActTanh, s, seg, B, glob ? W.rowb : nullptr, !glob);
+  if (precision == 1 && astp_fused_on) {
+    // linear2 + softmax over frames + attentive mean / std in one pass (astp_fused.hip)
+    AstpArgs a{W.att, xp, 1536, B, T, 1536, seg, pool2_frag, pool2.bias, 1e-7f, W.pooled};
+    run("astp", 2.0 * M * 1536 * 128, s, [&] { launch_astp_fused(a, s); });
+  } else {
+    gemm("pool_linear2", pool2, W.att, 128, W.logit, 1536, M, T, 1, 0, kActNone, s, seg, B);
+    run("astp", 0, s, [&] { launch_astp_pool(W.logit, xp, B, T, 1536, W.pooled, s, seg); });
+  }
+  run("head", 0, s, [&] {
+    launch_small_linear({W.pooled, 3072, head.wt, head.bias, embed, embed_dim, B, 3072, embed_dim, 0}, s);
+  });
+}
+
+}  // namespace wsp

@@ -162,8 +162,8 @@ void Model::Impl::finalize_hubert() {
           wf[(size_t)n * kHidden + k] = wv * g1[k];
           bb += (double)wv * be1[k];
           const float x = wf[(size_t)n * kHidden + k];
-          const uint16_t h = f2bf(x);
-          c += (double)bf2f(h) + (double)bf2f(f2bf(x - bf2f(h)));
+          const uint16_t h = pack::f2bf(x);
+          c += (double)pack::bf2f(h) + (double)pack::bf2f(pack::f2bf(x - pack::bf2f(h)));
         }
         bf[n] = (float)bb;
         cs[n] = (float)c;
@@ -246,7 +246,7 @@ HubertPlan Model::Impl::hubert_plan(int B, const int* lens) const {
     for (int k = 0; k < 7; ++k) T[k][b] = t = (t - kConvK[k]) / kConvS[k] + 1;
     Tout[b] = (lens[b] + kDownsample - 1) / kDownsample;
   }
-  const size_t cap = ((size_t)1 << 31) / 8 * 7 / (kConvDim * sizeof(float));  // conv0 rows per chunk
+  const size_t cap = kOperandCap / (kConvDim * sizeof(float));  // conv0 rows per chunk
   for (int b0 = 0; b0 < B;) {
     size_t rows = 0;
     int b1 = b0;
@@ -292,46 +292,56 @@ HubertPlan Model::Impl::hubert_plan(int B, const int* lens) const {
   pl.maxT6 = *std::max_element(T[6].begin(), T[6].end());
   // layers 4..6 batch-wide: more than one chunk, level-3 rows within a 2 GiB operand, and the
   // chunk buffers (free after the chunk loop) large enough for the level-4 / level-5 rows
-  pl.tail_batch = tail_batch && pl.chunks.size() > 1 && pl.M3 * kConvDim * sizeof(float) < ((size_t)1 << 31) / 8 * 7 &&
+  pl.tail_batch = tail_batch && pl.chunks.size() > 1 && pl.M3 * kConvDim * sizeof(float) < kOperandCap &&
                   pl.M4 <= pl.maxA && pl.M5 <= pl.maxB;
   WSP_CHECK(pl.M * kFfn * sizeof(float) < ((size_t)1 << 31) - 64,
             "HuBERT batch too large for one call (frames * 3072 floats must stay below 2 GiB)");
   return pl;
 }
 
-size_t Model::Impl::hubert_ws_floats(const HubertPlan& pl, size_t* offs) const {
+namespace {
+struct HubertWs {
+  float *cnnA, *cnnB;  // feature-extractor ping-pong of the largest chunk
+  double* stats;       // conv0 partial moments (f64)
+  float *x, *x1, *qkv, *ao, *ffn;
+  int* dseg;    // the plan's int32 offset tables
+  float* lnst;  // LN1 row statistics: [M][6] (mean, M2) of 128-column pieces
+  float* cnn3;  // tail_batch: [M3][512] level-3 rows of the whole batch
+  float* gate;  // WavLM: [M][12] gate of the layer in flight
+  size_t floats;
+};
+HubertWs hubert_ws(const HubertPlan& pl, bool wavlm, float* base) {
   const size_t M = pl.M;
-  const size_t sizes[] = {pl.maxA * kConvDim, pl.maxB * kConvDim, 2 * pl.maxStats,  // cnnA, cnnB, stats (f64)
-                          M * kHidden,        M * kHidden,        M * 3 * kHidden,                     // x, x1, qkv
-                          M * kHidden,        M * kFfn,                                                // ao, ffn / pos
-                          pl.offs.size(),                                                              // int32 offsets
-                          M * (kHidden / 128) * 2,                                                     // LN partials
-                          pl.tail_batch ? pl.M3 * kConvDim : 0,                                        // level-3 rows
-                          wavlm ? M * kHeads : 0};                                                     // WavLM gate
-  size_t o = 0;
-  for (int i = 0; i < 12; ++i) {
-    if (offs) offs[i] = o;
-    o += (sizes[i] + 63) / 64 * 64;
-  }
-  return o;
+  WsCursor c{base};
+  HubertWs w;
+  w.cnnA = c.take(pl.maxA * kConvDim);
+  w.cnnB = c.take(pl.maxB * kConvDim);
+  w.stats = reinterpret_cast<double*>(c.take(2 * pl.maxStats));
+  w.x = c.take(M * kHidden);
+  w.x1 = c.take(M * kHidden);
+  w.qkv = c.take(M * 3 * kHidden);
+  w.ao = c.take(M * kHidden);
+  w.ffn = c.take(M * kFfn);
+  w.dseg = reinterpret_cast<int*>(c.take(pl.offs.size()));
+  w.lnst = c.take(M * (kHidden / 128) * 2);
+  w.cnn3 = c.take(pl.tail_batch ? pl.M3 * kConvDim : 0);
+  w.gate = c.take(wavlm ? M * kHeads : 0);
+  w.floats = c.off;
+  return w;
 }
+}  // namespace
+
+size_t Model::Impl::hubert_ws_floats(const HubertPlan& pl) const { return hubert_ws(pl, wavlm, nullptr).floats; }
 
 void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws,
                                  hipStream_t s) {
-  size_t off[12];
-  hubert_ws_floats(pl, off);
-  float* cnnA = ws + off[0];
-  float* cnnB = ws + off[1];
-  double* stats = reinterpret_cast<double*>(ws + off[2]);
-  float* x = ws + off[3];
-  float* x1 = ws + off[4];
-  float* qkv = ws + off[5];
-  float* ao = ws + off[6];
-  float* ffn = ws + off[7];
+  const HubertWs W = hubert_ws(pl, wavlm, ws);
+  float *cnnA = W.cnnA, *cnnB = W.cnnB, *x = W.x, *x1 = W.x1, *qkv = W.qkv, *ao = W.ao, *ffn = W.ffn;
+  double* stats = W.stats;
   float* cnn6 = qkv;  // [M][512] CNN output of the whole batch; qkv is first written by layer 0
   float* pc = ffn;  // the pos_conv output is consumed before fc1 writes
-  int* dseg = reinterpret_cast<int*>(ws + off[8]);
-  float* lnst = ws + off[9];  // LN1 row statistics: [M][6] (mean, M2) of 128-column pieces
+  int* dseg = W.dseg;
+  float *lnst = W.lnst, *cnn3 = W.cnn3, *gate = W.gate;
   // pageable source: the copy is staged before hipMemcpyAsync returns, so pl.offs may go away
   WSP_HIP(hipMemcpyAsync(dseg, pl.offs.data(), pl.offs.size() * sizeof(int), hipMemcpyHostToDevice, s));
   const int B = pl.B;
@@ -341,37 +351,21 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
   const int* gseg3 = dseg + 2 * (B + 1);  // [B+1] batch-wide rows of conv levels 3, 4, 5
   const int* gseg4 = dseg + 3 * (B + 1);
   const int* gseg5 = dseg + 4 * (B + 1);
-  float* cnn3 = ws + off[10];       // tail_batch: [M3][512] level-3 rows of the whole batch
-  float* gate = ws + off[11];       // WavLM: [M][12] gate of the layer in flight
 
   auto conv = [&](const char* tag, const ConvW& cw, const float* a, int lda, float* out, int ldo, int rows, int Ti,
                   int stride, int pad, int act, const float* res, bool bias, const int* oseg, const int* iseg, int nseg,
                   int gcols = 0, int gcin = 0, const ConvGemmArgs* lnf = nullptr) {
-    ConvGemmArgs g{};
-    if (lnf) {  // LayerNorm fold fields
-      g.lnmode = lnf->lnmode;
-      g.ln_out = lnf->ln_out;
-      g.ln_in = lnf->ln_in;
-      g.ln_parts = lnf->ln_parts;
-      g.ln_cs = lnf->ln_cs;
-      g.ln_g = lnf->ln_g;
-      g.ln_b = lnf->ln_b;
-      g.ln_eps = lnf->ln_eps;
-    }
-    g.a[0] = g.a[1] = g.a[2] = a;
-    g.lda[0] = g.lda[1] = g.lda[2] = lda;
-    g.cseg[0] = 0;
-    g.cseg[1] = g.cseg[2] = g.cseg[3] = cw.cin;
-    fill(g, cw, rows, 1, 1, pad, out, ldo, act, nullptr, bias);
+    ConvGemmArgs g = lnf ? *lnf : ConvGemmArgs{};  // lnf carries the LayerNorm fold fields only
+    one_operand(g, a, lda, cw.cin);
+    // taps == 1 projections pass oseg null: row-local, no utterance structure needed
+    fill(g, cw, rows, 1, 1, pad, out, ldo, act, nullptr, bias, oseg, nseg);
     g.stride = stride;
     g.Ti = oseg ? Ti : 1;  // row-local (taps 1) GEMMs: uniform T = Ti = 1 so input row == output row
     g.res = res;
     g.ldres = res ? ldo : 0;
     g.gcols = gcols;
     g.gcin = gcin;
-    g.seg = oseg;  // taps==1 projections pass null: row-local, no utterance structure needed
     g.iseg = iseg;
-    g.nseg = nseg;
     // x3_variant 5 only: the long-K / GELU GEMMs (CNN, fc1, fc2) on the 16x16x32 form of the 256 x 256
     // tile (r3 A/B: CNN -2 %, fc1 -3 %, fc2 -6 % per launch), QKV / out_proj on 32x32.  Under the
     // default 7 (and 8) every one of these GEMMs (N % 256 == 0) takes the LDS-DMA 16x16x32 tile, which
@@ -531,7 +525,7 @@ size_t Model::frontend_workspace_bytes_segments(int B, const int* lens) const {
   size_t bytes = 256;
   for (int i = 0; i < ns; ++i) {
     const int b0 = B * i / ns, b1 = B * (i + 1) / ns;
-    bytes += (impl->hubert_ws_floats(impl->hubert_plan(b1 - b0, lens + b0), nullptr) * sizeof(float) + 255) &
+    bytes += (impl->hubert_ws_floats(impl->hubert_plan(b1 - b0, lens + b0)) * sizeof(float) + 255) &
              ~size_t(255);
   }
   return bytes;
@@ -575,7 +569,7 @@ void Model::forward_frontend_segments(const float* wav, int B, const int* lens, 
   for (int i = 0; i < ns; ++i) {
     const HubertPlan& pl = pls[i];
     m.forward_hubert(wav + sample0, pl, feats + frame0 * kHidden, cmn, reinterpret_cast<float*>(wsb), m.sub(s, i));
-    wsb += (m.hubert_ws_floats(pl, nullptr) * sizeof(float) + 255) & ~size_t(255);
+    wsb += (m.hubert_ws_floats(pl) * sizeof(float) + 255) & ~size_t(255);
     for (int b = B * i / ns; b < B * (i + 1) / ns; ++b) sample0 += lens[b];
     frame0 += pl.Mout;
   }

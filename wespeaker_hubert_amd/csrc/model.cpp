@@ -1,21 +1,156 @@
-// Speaker-model runtime: parameter intake (reference state_dict order),
-// BatchNorm folding + weight packing on the host in f64, device residency,
-// and the forward schedule of HIP kernels over a caller-provided workspace.
-//
-// ECAPA-TDNN forward = wespeaker/models/ecapa_tdnn.py:208-234, channels-last:
-//   layer1  Conv1dReluBn(F->C, k5)                        -> x1   [M][C]
-//   layerL  SE_Res2Block(dil L):  c1 (1x1) -> h1
-//           Res2 chain i=0..6: conv_k3(h1_i (+ h2_{i-1})) -> h2_i  (7 GEMMs)
-//           c3 (1x1) over cat(h2_0..6, h1_7)             -> h3   (no copy)
-//           SE: frame mean -> FC relu -> FC sigmoid -> x_{L} + h3 * g
-//   conv    1x1 over cat(x2, x3, x4) (no copy), ReLU      -> xp   [M][1536]
-//   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
-//           -> online-softmax attentive mean/std          -> [B][3072]
-//   head    BN(3072) + Linear (+ bn2) folded into one GEMV -> embed [B][D]
+// Speaker-model runtime, the part every family shares: the Model API, parameter intake
+// (reference state_dict order), pack-and-upload helpers (BatchNorm folding and packing run on
+// the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
+// The families' tables, folds, workspace layouts and forward schedules are in ecapa_model.cpp,
+// resnet_model.cpp (ResNet and SimAM-ResNet) and hubert_model.cpp.
 #include "model_impl.h"
 
 namespace wsp {
 
+int detail::chunk_for(int B, size_t bytes) {
+  const int bc = std::min((int)std::max<size_t>(1, kOperandCap / bytes), B);
+  const int chunks = (B + bc - 1) / bc;
+  return (B + chunks - 1) / chunks;
+}
+
+// ------------------------------------------------------ parameter table ---
+void Model::Impl::add(const std::string& n, std::vector<int64_t> shape) {
+  idx[n] = (int)params.size();
+  params.push_back(Param{n, std::move(shape), {}, false});
+}
+void Model::Impl::add_bn(const std::string& p, int64_t c) {
+  add(p + ".weight", {c});
+  add(p + ".bias", {c});
+  add(p + ".running_mean", {c});
+  add(p + ".running_var", {c});
+  add(p + ".num_batches_tracked", {});
+}
+const std::vector<float>& Model::Impl::P(const std::string& n) const {
+  auto it = idx.find(n);
+  WSP_CHECK(it != idx.end(), "missing parameter " + n);
+  const Param& p = params[it->second];
+  WSP_CHECK(p.set || p.numel() == 0, "parameter not set: " + n);
+  return p.host;
+}
+
+void Model::Impl::bn_affine(const std::string& p, std::vector<double>& sc, std::vector<double>& sh) const {
+  const auto& w = P(p + ".weight");
+  const auto& b = P(p + ".bias");
+  const auto& rm = P(p + ".running_mean");
+  const auto& rv = P(p + ".running_var");
+  sc.resize(w.size());
+  sh.resize(w.size());
+  for (size_t i = 0; i < w.size(); ++i) {
+    sc[i] = (double)w[i] / std::sqrt((double)rv[i] + kBnEps);
+    sh[i] = (double)b[i] - (double)rm[i] * sc[i];
+  }
+}
+
+// ------------------------------------------------------ pack and upload ---
+ConvW Model::Impl::pack_conv(const std::vector<float>& w, int N, int cin, int taps, const float* bias,
+                             const std::string& bn) {
+  ConvW cw;
+  cw.N = N;
+  cw.cin = cin;
+  cw.taps = taps;
+  cw.K = cin * taps;
+  cw.Kp = round_up(cw.K, 64);  // even number of 32-wide k-tiles (bf16x3 pipeline)
+  const std::vector<float> packed = pack::conv_kmajor(w, N, cin, taps, cw.Kp);
+  std::vector<uint16_t> hi, lo;
+  pack::split(packed, hi, lo);
+  cw.w = dev.upload(packed);
+  cw.whi = dev.upload_u16(hi);
+  cw.wlo = dev.upload_u16(lo);
+  if (bias) cw.bias = dev.upload(std::vector<float>(bias, bias + N));
+  if (!bn.empty()) {
+    std::vector<double> sc, sh;
+    bn_affine(bn, sc, sh);
+    cw.scale = dev.upload(std::vector<float>(sc.begin(), sc.end()));
+    cw.shift = dev.upload(std::vector<float>(sh.begin(), sh.end()));
+  }
+  return cw;
+}
+
+LinW Model::Impl::pack_lin(const float* w, int N, int K, int ldk, const float* bias) {
+  LinW lw;
+  lw.N = N;
+  lw.K = K;
+  lw.wt = dev.upload(pack::transpose(w, N, K, ldk));
+  if (bias) lw.bias = dev.upload(std::vector<float>(bias, bias + N));
+  return lw;
+}
+
+// -------------------------------------------------------------- launches ---
+void Model::Impl::one_operand(ConvGemmArgs& g, const float* a, int lda, int cin) {
+  g.a[0] = g.a[1] = g.a[2] = a;
+  g.lda[0] = g.lda[1] = g.lda[2] = lda;
+  g.cseg[0] = 0;
+  g.cseg[1] = g.cseg[2] = g.cseg[3] = cin;
+}
+
+void Model::Impl::fill(ConvGemmArgs& g, const ConvW& cw, int M, int T, int dil, int pad, float* out, int ldo, int act,
+                       const float* row_bias, bool use_bias, const int* seg, int nseg) {
+  g.cin = cw.cin;
+  g.taps = cw.taps;
+  g.dil = dil;
+  g.pad = pad;
+  g.M = M;
+  g.T = T;
+  g.N = cw.N;
+  g.w = cw.w;
+  g.K = cw.K;
+  g.Kp = cw.Kp;
+  g.bias = use_bias ? cw.bias : nullptr;
+  g.row_bias = row_bias;
+  g.scale = cw.scale;
+  g.shift = cw.shift;
+  g.out = out;
+  g.ldo = ldo;
+  g.act = act;
+  g.seg = seg;
+  g.nseg = nseg;
+}
+
+void Model::Impl::launch(const ConvGemmArgs& g, const ConvW& cw, hipStream_t s) {
+  if (precision == 1)
+    launch_conv_gemm_x3(g, cw.whi, cw.wlo, x3_variant, s);
+  else
+    launch_conv_gemm(g, s);
+}
+
+void Model::Impl::gemm(const char* tag, const ConvW& cw, const float* a0, int lda, float* out, int ldo, int M, int T,
+                       int dil, int pad, int act, hipStream_t s, const int* seg, int nseg, const float* row_bias,
+                       bool use_bias, int role) {
+  ConvGemmArgs g{};
+  one_operand(g, a0, lda, cw.cin);
+  g.role = role;
+  fill(g, cw, M, T, dil, pad, out, ldo, act, row_bias, use_bias, seg, nseg);
+  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch(g, cw, s); });
+}
+
+// --------------------------------------------------- sub-batch streams ---
+void Model::Impl::fork(hipStream_t s, int ns) {
+  while ((int)sub_st.size() < ns - 1) {
+    hipStream_t t;
+    WSP_HIP(hipStreamCreateWithFlags(&t, hipStreamNonBlocking));
+    sub_st.push_back(t);
+  }
+  while ((int)sub_ev.size() < ns) {
+    hipEvent_t e;
+    WSP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    sub_ev.push_back(e);
+  }
+  WSP_HIP(hipEventRecord(sub_ev[0], s));
+  for (int i = 1; i < ns; ++i) WSP_HIP(hipStreamWaitEvent(sub_st[i - 1], sub_ev[0], 0));
+}
+void Model::Impl::join(hipStream_t s, int ns) {
+  for (int i = 1; i < ns; ++i) {
+    WSP_HIP(hipEventRecord(sub_ev[i], sub_st[i - 1]));
+    WSP_HIP(hipStreamWaitEvent(s, sub_ev[i], 0));
+  }
+}
+
+// ------------------------------------------------------------ Model API ---
 Model::Model() : impl(new Impl) {}
 Model::~Model() {
   for (auto& kv : impl->prof_map)
@@ -148,9 +283,7 @@ int Model::feat_dim() const { return impl->feat_dim; }
 // workspace of one sub-batch of B utterances, 256-byte granules
 size_t Model::Impl::ws_bytes_one(int B, int T) const {
   const int bc = ecapa ? ecapa_chunk(B, T) : B;
-  const size_t f = ecapa   ? ecapa_ws_floats(bc, (size_t)bc * T, nullptr)
-                   : simam ? simam_ws_floats(B, T, nullptr)
-                           : resnet_ws_floats(B, T, nullptr);
+  const size_t f = ecapa ? ecapa_ws_floats(bc, (size_t)bc * T) : resnet_ws_floats(B, T);
   return (f * sizeof(float) + 255) & ~size_t(255);
 }
 
@@ -199,7 +332,7 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
 size_t Model::workspace_bytes_segments(int B, int M) const {
   WSP_CHECK(impl->ecapa, "segmented batches are implemented for ECAPA-TDNN handles");
   WSP_CHECK(B > 0 && M >= B, "segmented batch needs B >= 1 and M >= B rows");
-  return impl->ecapa_ws_floats(B, (size_t)M, nullptr) * sizeof(float) + 256;
+  return impl->ecapa_ws_floats(B, (size_t)M) * sizeof(float) + 256;
 }
 
 void Model::forward_segments(const float* feats, int B, const int* seg, int M, float* embed, void* ws,
@@ -223,101 +356,78 @@ void Model::profile(bool on) {
   impl->prof = on;
 }
 
-void Model::set_option(const std::string& key, int value) {
-  if (key == "precision") {
-    WSP_CHECK(value == 0 || value == 1, "precision must be 0 (f32) or 1 (bf16x3)");
-    impl->precision = value;
-  } else if (key == "layer") {
-    WSP_CHECK(impl->hubert, "option 'layer' applies to the HuBERT front end");
-    WSP_CHECK(!impl->finalized, "option 'layer' must be set before finalize");
-    WSP_CHECK(value >= -1 && value <= 12, "layer must be -1 (weighted sum) or 0..12");
-    impl->h_layer_sel = value;
-  } else if (key == "in_planes") {
-    WSP_CHECK(impl->simam, "option 'in_planes' applies to SimAM-ResNet handles");
-    WSP_CHECK(!impl->finalized, "option 'in_planes' must be set before finalize");
-    WSP_CHECK(value == 32 || value == 64, "in_planes must be 32 or 64");
-    for (const auto& p : impl->params) WSP_CHECK(!p.set, "option 'in_planes' must be set before the weights");
-    impl->m_ch = value;
-    impl->build_simam_params();
-  } else if (key == "res_prefetch") {
-    WSP_CHECK(value == 0 || value == 1, "res_prefetch must be 0 or 1");
-    impl->res_prefetch = value;
-  } else if (key == "c1_stage_fuse") {
-    WSP_CHECK(value == 0 || value == 1, "c1_stage_fuse must be 0 or 1");
-    impl->c1_stage_fuse = value;
-  } else if (key == "sc_fuse") {
-    WSP_CHECK(value >= 0 && value <= 3, "sc_fuse must be 0 .. 3 (bit 0: one GEMM, bit 1: in the tail)");
-    impl->sc_fuse = value;
-  } else if (key == "res_tail") {
-    WSP_CHECK(value >= 0 && value <= 2, "res_tail must be 0 (off), 1 (tail + next conv1) or 2 (tail alone)");
-    impl->res_tail = value;
-  } else if (key == "cat_gate") {
-    WSP_CHECK(value == 0 || value == 1, "cat_gate must be 0 or 1");
-    impl->cat_gate = value;
-  } else if (key == "res2_fused") {
-    WSP_CHECK(value == 0 || value == 1, "res2_fused must be 0 or 1");
-    impl->res2_fused = value;
-  } else if (key == "attn_pipe") {
-    WSP_CHECK(value == 0 || value == 1, "attn_pipe must be 0 or 1");
-    impl->attn_pipe = value;
-  } else if (key == "pos_conv") {
-    WSP_CHECK(value == 0 || value == 1, "pos_conv must be 0 (grouped implicit GEMM) or 1 (direct grouped conv)");
-    impl->pos_conv = value;
-  } else if (key == "ln_fold") {
-    WSP_CHECK(value == 0 || value == 1, "ln_fold must be 0 (LayerNorm kernels) or 1 (folded into the GEMMs)");
-    impl->ln_fold = value;
-  } else if (key == "tail_batch") {
-    WSP_CHECK(value == 0 || value == 1, "tail_batch must be 0 (CNN layers 4-6 per chunk) or 1 (batch-wide)");
-    impl->tail_batch = value;
-  } else if (key == "astp_fused") {
-    WSP_CHECK(value >= 0 && value <= 3, "astp_fused must be 0 (linear2 GEMM + pooling kernel) or 1 (fused)");
-    impl->astp_fused_on = value ? 1 : 0;  // 2 / 3: former fused variants (r3 pruned), deprecated aliases of 1
-  } else if (key == "conv3x3_img") {
-    WSP_CHECK(value >= 0 && value <= 3, "conv3x3_img must be 0 (off), 1 (32 / 64 channels) or 2 / 3 (also 128)");
-    impl->conv3x3_img_on = value;
-  } else if (key == "streams") {
-    WSP_CHECK(value >= 1 && value <= 8, "streams must be 1..8");
-    impl->streams = value;
-  } else if (key == "res2_variant") {
-    WSP_CHECK(value == 0 || value == 2 || value == 3 || value == 4,
-              "res2_variant must be 0 (4 waves, 2 x 2), 2 (4 waves on N, 4 W k-steps in flight), 3 (8 waves) "
-              "or 4 (halo-free strips, c1024 widths; else as 3)");
-    impl->res2_variant = value;
-  } else if (key == "x3_variant") {
-    WSP_CHECK((value >= 0 && value <= 9),
-              "x3_variant must be 3, 4, 5, 6 (5 on 16x16x32 MFMAs) or 7 (6 staged by LDS-DMA)");
-    // 0 / 1 (unswizzled tiles), 2 / 9 (the r2 LDS-DMA tiles): pruned in r3; 8 (the r5 ping-pong form
-    // of 7, bit-identical and slower): pruned in r5 — deprecated aliases of 5 / 7
-    impl->x3_variant = value >= 3 && value <= 7 ? value : value == 8 ? 7 : 5;
-  } else if (key == "attn_lds" || key == "conv1x1_rows") {
-    // pruned in r3 (hubert.hip's streaming mha_kernel, conv1x1_rows.hip): accepted, no effect
-  } else {
-    throw InvalidArg{"unknown option " + key};
-  }
-}
-
-int Model::get_option(const std::string& key) const {
-  const Impl& m = *impl;
-  if (key == "precision") return m.precision;
-  if (key == "streams") return m.streams;
-  if (key == "layer") return m.h_layer_sel;
-  if (key == "in_planes") return m.m_ch;
-  if (key == "res2_fused") return m.res2_fused;
-  if (key == "cat_gate") return m.cat_gate;
-  if (key == "res_prefetch") return m.res_prefetch;
-  if (key == "res_tail") return m.res_tail;
-  if (key == "sc_fuse") return m.sc_fuse;
-  if (key == "c1_stage_fuse") return m.c1_stage_fuse;
-  if (key == "astp_fused") return m.astp_fused_on;
-  if (key == "attn_pipe") return m.attn_pipe;
-  if (key == "pos_conv") return m.pos_conv;
-  if (key == "ln_fold") return m.ln_fold;
-  if (key == "tail_batch") return m.tail_batch;
-  if (key == "res2_variant") return m.res2_variant;
-  if (key == "x3_variant") return m.x3_variant;
-  if (key == "conv3x3_img") return m.conv3x3_img_on;
+// One table behind set_option and get_option: key, Impl member, accepted range [lo, hi] without
+// `hole`, and the refusal's message.
+namespace {
+struct Opt {
+  const char* key;
+  int Model::Impl::*field;
+  int lo, hi, hole;
+  const char* err;
+};
+using I = Model::Impl;
+constexpr int kNoHole = -1000;
+const Opt kOpts[] = {
+    {"precision", &I::precision, 0, 1, kNoHole, "precision must be 0 (f32) or 1 (bf16x3)"},
+    {"streams", &I::streams, 1, 8, kNoHole, "streams must be 1..8"},
+    {"layer", &I::h_layer_sel, -1, 12, kNoHole, "layer must be -1 (weighted sum) or 0..12"},
+    {"in_planes", &I::m_ch, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
+    {"res2_fused", &I::res2_fused, 0, 1, kNoHole, "res2_fused must be 0 or 1"},
+    {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
+    {"res_prefetch", &I::res_prefetch, 0, 1, kNoHole, "res_prefetch must be 0 or 1"},
+    {"res_tail", &I::res_tail, 0, 2, kNoHole, "res_tail must be 0 (off), 1 (tail + next conv1) or 2 (tail alone)"},
+    {"sc_fuse", &I::sc_fuse, 0, 3, kNoHole, "sc_fuse must be 0 .. 3 (bit 0: one GEMM, bit 1: in the tail)"},
+    {"c1_stage_fuse", &I::c1_stage_fuse, 0, 1, kNoHole, "c1_stage_fuse must be 0 or 1"},
+    {"astp_fused", &I::astp_fused_on, 0, 3, kNoHole,
+     "astp_fused must be 0 (linear2 GEMM + pooling kernel) or 1 (fused)"},
+    {"attn_pipe", &I::attn_pipe, 0, 1, kNoHole, "attn_pipe must be 0 or 1"},
+    {"pos_conv", &I::pos_conv, 0, 1, kNoHole,
+     "pos_conv must be 0 (grouped implicit GEMM) or 1 (direct grouped conv)"},
+    {"ln_fold", &I::ln_fold, 0, 1, kNoHole, "ln_fold must be 0 (LayerNorm kernels) or 1 (folded into the GEMMs)"},
+    {"tail_batch", &I::tail_batch, 0, 1, kNoHole,
+     "tail_batch must be 0 (CNN layers 4-6 per chunk) or 1 (batch-wide)"},
+    {"res2_variant", &I::res2_variant, 0, 4, 1,
+     "res2_variant must be 0 (4 waves, 2 x 2), 2 (4 waves on N, 4 W k-steps in flight), 3 (8 waves) "
+     "or 4 (halo-free strips, c1024 widths; else as 3)"},
+    {"x3_variant", &I::x3_variant, 0, 9, kNoHole,
+     "x3_variant must be 3, 4, 5, 6 (5 on 16x16x32 MFMAs) or 7 (6 staged by LDS-DMA)"},
+    {"conv3x3_img", &I::conv3x3_img_on, 0, 3, kNoHole,
+     "conv3x3_img must be 0 (off), 1 (32 / 64 channels) or 2 / 3 (also 128)"},
+};
+const Opt& find_opt(const std::string& key) {
+  for (const Opt& o : kOpts)
+    if (key == o.key) return o;
   throw InvalidArg{"unknown option " + key};
 }
+}  // namespace
+
+void Model::set_option(const std::string& key, int value) {
+  Impl& m = *impl;
+  // pruned in r3 (hubert.hip's streaming mha_kernel, conv1x1_rows.hip): accepted, no effect
+  if (key == "attn_lds" || key == "conv1x1_rows") return;
+  const Opt& o = find_opt(key);
+  if (key == "layer") {
+    WSP_CHECK(m.hubert, "option 'layer' applies to the HuBERT front end");
+    WSP_CHECK(!m.finalized, "option 'layer' must be set before finalize");
+  } else if (key == "in_planes") {
+    WSP_CHECK(m.simam, "option 'in_planes' applies to SimAM-ResNet handles");
+    WSP_CHECK(!m.finalized, "option 'in_planes' must be set before finalize");
+    WSP_CHECK(value == 32 || value == 64, o.err);
+    for (const auto& p : m.params) WSP_CHECK(!p.set, "option 'in_planes' must be set before the weights");
+  }
+  WSP_CHECK(value >= o.lo && value <= o.hi && value != o.hole, o.err);
+  if (key == "x3_variant") {
+    // 0 / 1 (unswizzled tiles), 2 / 9 (the r2 LDS-DMA tiles): pruned in r3; 8 (the r5 ping-pong form
+    // of 7, bit-identical and slower): pruned in r5 — deprecated aliases of 5 / 7
+    value = value >= 3 && value <= 7 ? value : value == 8 ? 7 : 5;
+  } else if (key == "astp_fused") {
+    value = value ? 1 : 0;  // 2 / 3: former fused variants (r3 pruned), deprecated aliases of 1
+  }
+  m.*o.field = value;
+  if (key == "in_planes") m.build_simam_params();  // the parameter table follows the stem width
+}
+
+int Model::get_option(const std::string& key) const { return impl->*find_opt(key).field; }
 
 void Model::profile_query(const std::string& tag, int* launches, double* total_ms, double* flops) {
   // `tag` names one kernel class or, as a prefix "tag.", every sub-class under it

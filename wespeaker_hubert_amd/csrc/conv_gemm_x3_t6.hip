@@ -802,8 +802,9 @@ void t_g256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t
     WSP_CHECK(am == 1 && !p.colsum && !p.row_bias && !p.scale && p.N % 128 == 0 &&
                   ((p.lnmode & 1) == 0 || (p.ln_out && p.res && p.act == kActNone)) &&
                   ((p.lnmode & 6) == 0 || (p.ln_in && p.ln_parts >= 1 && p.ln_parts <= kLnMaxParts)) && ((p.lnmode & 2) == 0 || (p.ln_cs && !p.res)) &&
+                  (p.lnmode != 2 || p.act == kActNone || p.act == kActGelu) &&  // the fold's two epilogue instances
                   ((p.lnmode & 4) == 0 || (p.ln_g && p.ln_b && p.res && p.act == kActNone)),
-              "conv_gemm_x3: LayerNorm fold needs a dense 1x1 GEMM and its operands");
+              "conv_gemm_x3: LayerNorm fold needs a dense 1x1 GEMM and its operands (fold: no activation or GELU)");
     switch (p.lnmode) {
       case 1: hipLaunchKernelGGL((conv_gemm_g<1, false, 1>), dim3(nwg), dim3(512), lds, s, p, h, l); break;
       case 2: hipLaunchKernelGGL((conv_gemm_g<1, false, 2>), dim3(nwg), dim3(512), lds, s, p, h, l); break;

@@ -76,6 +76,8 @@ struct ConvGemmArgs {
   // (A = the un-normalised rows, W pre-scaled by gamma, bias = b + W beta); 4 = the residual
   // is normalised on the fly: res = (res - mu) rstd ln_g + ln_b.  Modes 2 / 4 read mu, rstd
   // from ln_in [M][ln_parts][2] (partials of 128 columns, ln_parts x 128 = the normalised width).
+  // Modes 1 / 4 / 5 take no activation, mode 2 none or GELU (others are refused); no scale / shift,
+  // row bias or column sums.
   int lnmode;
   float* ln_out;
   const float* ln_in;

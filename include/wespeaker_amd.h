@@ -206,6 +206,11 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *   "cat_gate"     ECAPA-TDNN: 1 = conv_cat on [out2, out3, out4 - out3] with weights
  *                  [W_a, W_b + W_c, W_c], so the last SE block stores only its gated branch
  *                  (default; equal to 0 up to rounding, ~1e-6), 0 = conv_cat on [out2, out3, out4]
+ *   "gate_fold"    ECAPA-TDNN with cat_gate 1: 1 = the gated branch is never stored; conv_cat
+ *                  reads the last block's conv3 output and multiplies it by the SE gate as it
+ *                  splits its A fragments (default; bit-identical to 0).  Effective at precision 1,
+ *                  x3_variant 7 on uniform batches of T >= 256 frames; ragged or shorter batches
+ *                  and the other kernels keep the gate pass.  0 = the gate pass throughout
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block

@@ -7,6 +7,10 @@
 // pruned: profiles/r5a_gemm_check.txt, r5m_gemm_family9.txt, r5p_gemm_persistent.txt; a staggered
 // start of every other CU's first block, r5ac_gemm_stagger_experiment.txt.)
 //   gemm_check [case|all] [reps] [variants, e.g. 67]
+// Case gate_seg (by name only; not part of "all"): family 7's gated instance (AM 4: the third A
+// segment multiplied by a per-utterance gate as its fragments are read) against residual_scale<false>
+// followed by the ungated instance, bit for bit, on 3 utterances of 300 frames (a tile straddling
+// two utterances, a partial last tile).
 // r6 experiment variants: 8 = family 7 with the A split replaced by a bit reinterpretation
 // (timing only: no split VALU, same LDS / DMA traffic; its outputs differ), 9 = family 7 with the
 // next tile's DMA pieces interleaved into the k-tile's quarters (bit-identical); 10 = family 7's
@@ -23,6 +27,7 @@
 #define WSP_G7_XP 1
 #include "../wespeaker_hubert_amd/csrc/conv_gemm_x3_t5.hip"
 #include "../wespeaker_hubert_amd/csrc/conv_gemm_x3_t6.hip"
+#include "../wespeaker_hubert_amd/csrc/ops.hip"  // residual_scale_kernel<false>: the gate pass of case gate_seg
 namespace wsp { namespace x3 {
 void t_4x2_2x4_sw1(const ConvGemmArgs&, const __bf16*, const __bf16*, hipStream_t) { std::abort(); }
 } }
@@ -202,6 +207,35 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   int bad = 0;
+  if (which == "gate_seg") {
+    const int B = 3, T = 300, C = 512, N = 1536;
+    Case c = make("gate_seg", B, T, T, 1, 3 * C, 1, 1, 0, N, kActRelu, false, false, false, false, 3, nullptr);
+    float* gate = dfill((size_t)B * C, 31, 0.f, 1.f, 0);
+    float *scaled, *ref, *got;
+    CK(hipMalloc(&scaled, (size_t)B * T * C * 4));
+    CK(hipMalloc(&ref, c.out_words * 4));
+    CK(hipMalloc(&got, c.out_words * 4));
+    CK(hipMemset(ref, 0xff, c.out_words * 4));
+    CK(hipMemset(got, 0xee, c.out_words * 4));
+    CK(hipDeviceSynchronize());
+    launch_residual_scale(nullptr, c.g.a[2], gate, scaled, B, T, C, s);
+    ConvGemmArgs q = c.g;
+    q.a[2] = scaled;
+    q.out = ref;
+    x3::t_g256(q, c.whi, c.wlo, s);
+    q = c.g;
+    q.gate = gate;
+    q.ldg = C;
+    q.gate_k0 = 2 * C;
+    q.out = got;
+    if (!x3::g256_gate_supported(q)) { std::fprintf(stderr, "gate_seg: the gated instance does not take these operands\n"); return 2; }
+    for (int r = 0; r < reps; ++r) x3::t_g256(q, c.whi, c.wlo, s);
+    CK(hipStreamSynchronize(s));
+    const unsigned long long d = ndiff(ref, got, c.out_words);
+    std::printf("gate_seg   family 7 gated vs residual_scale + family 7: %llu of %zu outputs differ\n", d, c.out_words);
+    std::printf(d ? "MISMATCH in 1 comparisons\n" : "all families bit-identical\n");
+    return d ? 1 : 0;
+  }
   for (const Case& c : cases) {
     std::vector<float*> out(13, nullptr);
     std::vector<double*> cs(13, nullptr);

@@ -52,6 +52,10 @@ void launch_colsum_mean(const double* part, int block_rows, int T, int B, int N,
   WSP_HIP(hipGetLastError());
 }
 
+bool conv_gemm_x3_gate_ok(const ConvGemmArgs& args, int variant) {
+  return variant == 7 && args.gate && x3::g256_gate_supported(normalized(args));
+}
+
 void launch_conv_gemm_x3(const ConvGemmArgs& args, const void* whi, const void* wlo, int variant,
                          hipStream_t s) {
   const ConvGemmArgs p = normalized(args);
@@ -70,6 +74,8 @@ void launch_conv_gemm_x3(const ConvGemmArgs& args, const void* whi, const void* 
             "conv_gemm_x3: the LayerNorm fold runs on tile family 7 only");
   WSP_CHECK(!p.sc2d || (variant == 7 && x3::g256_supported(p)),
             "conv_gemm_x3: conv3 + shortcut runs on tile family 7 only (N % 256 == 0, 16-B aligned operands)");
+  WSP_CHECK(!p.gate || (variant == 7 && x3::g256_gate_supported(p)),
+            "conv_gemm_x3: the gated A tail runs on tile family 7 only (conv_gemm_x3_gate_ok)");
   if (variant == 7 && x3::g256_supported(p)) {
     // variant 7 (r4): the 256 x 256 16x16x32 tile with every operand staged by LDS-DMA and the
     // fp32 A split at fragment time (conv_gemm_x3_t6.hip); bit-identical to 6, which serves

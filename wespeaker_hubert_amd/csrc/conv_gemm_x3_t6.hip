@@ -318,7 +318,14 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
                                                       const __bf16* __restrict__ wlo) {
   using L = Lds<true, 16>;
   // AM 3: AM 1 whose A segment 1 is the projection shortcut's 2-D strided input (ConvGemmArgs::sc2d)
-  constexpr bool DENSE = AM == 1 || AM == 3;
+  // AM 4: AM 1 whose A is multiplied by a per-utterance gate from k = gate_k0 on (ConvGemmArgs::gate):
+  // the gate rows of the block's two utterances sit in LDS behind the two stages, the k-loop runs
+  // as an ungated loop followed by a gated one, and a gated tile's rdA multiplies its fp32 values
+  // by the row's utterance's gate chunk before the split (h * g rounded to fp32, as
+  // residual_scale_kernel<false> stored it: same split, same MFMA order, bit-identical results)
+  constexpr bool DENSE = AM == 1 || AM == 3 || AM == 4;
+  constexpr bool GATE = AM == 4;
+  static_assert(!GATE || (!CSK && LNM == 0 && XP == 0), "the gated instance: plain epilogues only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -431,12 +438,24 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 ah[2], al[2], bh[4], bl[4];
-  auto rdA = [&](const unsigned char* st, int ih) {  // fp32 rows -> bf16 hi / lo fragments
+  // gated tiles (AM 4): gp = this lane's 8 gate values of the tile in utterance slot 0 (the
+  // utterance of the block's first row); rows from g_nb on belong to slot 1, g_slot bytes further
+  const int g_nb = GATE ? min((m0 / p.T + 1) * p.T, p.M) - m0 : 0;
+  const int g_slot = GATE ? (p.K - p.gate_k0) * 4 : 0;
+  auto rdA = [&](auto gated, const unsigned char* st, int ih, const unsigned char* gp = nullptr) {
+    // fp32 rows -> bf16 hi / lo fragments (no contraction: the gated product is rounded to fp32
+    // before the lo term's subtraction, as the stored g * h was)
+#pragma clang fp contract(off)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int r = wm * 64 + (ih * 2 + i) * 16 + r16;
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk));
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk + 1));
+      f32x4 x0 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk));
+      f32x4 x1 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk + 1));
+      if constexpr (decltype(gated)::value) {
+        const unsigned char* gr = gp + (r >= g_nb ? g_slot : 0);
+        x0 = x0 * *reinterpret_cast<const f32x4*>(gr);
+        x1 = x1 * *reinterpret_cast<const f32x4*>(gr + 16);
+      }
       if constexpr (XP == 1 || XP == 4) {
         ah[i] = __builtin_bit_cast(bf16x8, x0);
         al[i] = __builtin_bit_cast(bf16x8, x1);
@@ -476,19 +495,37 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   // behind tile 0's) and held through the k-loop (2 registers)
   float lmu = 0.f, lrs = 1.f;
   if constexpr ((LNM & 6) != 0) g_ln_row(p, min(m0 + wm * 64 + lane, p.M - 1), lmu, lrs);
+  if constexpr (GATE) {
+    // the gate rows of utterances m0 / T and m0 / T + 1 (zeros past the batch) -> LDS behind the
+    // stages, slot u at u * g_slot: 1-KB wave pieces issued ahead of tile 0's DMAs, so the first
+    // counted wait below covers them (waves with no piece only have fewer operations outstanding)
+    const int ppu = g_slot >> 10, b0 = m0 / p.T;  // pieces per utterance (g_slot % 1024 == 0)
+    const __amdgpu_buffer_rsrc_t rg = make_rsrc(p.gate);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // 2 g_slot <= 32 KB: at most 4 pieces per wave
+      const int q = 8 * i + wave;
+      if (q >= 2 * ppu) break;
+      const int u = q >= ppu ? 1 : 0;
+      const bool ok = (b0 + u) * p.T < p.M;
+      g_dma(rg, smem + 2 * kGStage + q * 1024, ok ? ((b0 + u) * p.ldg + (q - u * ppu) * 256 + lane * 4) * 4 : kOOB);
+    }
+  }
   dma(0, 0);
   dma(1, 1);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile 0 landed (8 DMAs per k-tile and lane)
   __builtin_amdgcn_s_barrier();
   // (XP 2 keeps this prologue: tile 1 is in flight, iteration 0 issues nothing, iteration kt >= 1
   // issues tile kt + 1 into the buffer tile kt - 1 left)
-  for (int kt = 0; kt < nk; ++kt) {
+  auto ktile = [&](auto gated, int kt) {
     const int buf = kt & 1;
     const unsigned char* st = smem + buf * kGStage;
+    // gated tiles: the lane's gate chunks 2 qk, 2 qk + 1 of this k-tile (slot 0)
+    const unsigned char* gp =
+        decltype(gated)::value ? smem + 2 * kGStage + (kt * BK - p.gate_k0 + 8 * qk) * 4 : nullptr;
     if constexpr (XP == 2) {
       // the next tile's pieces go out between this tile's quarters (the other buffer is free:
       // every wave passed the barrier that ended tile kt - 1's reads of it)
-      rdA(st, 0);
+      rdA(gated, st, 0);
       rdB(st, 0);
       mm(0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -499,35 +536,40 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
       __builtin_amdgcn_sched_barrier(0);
       if (kt >= 1 && kt + 1 < nk) dma(kt + 1, buf ^ 1, 2);
       __builtin_amdgcn_sched_barrier(0);
-      rdA(st, 1);
+      rdA(gated, st, 1);
       mm(1, 1);
       rdB(st, 0);
       mm(1, 0);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      continue;
+      return;
     }
     // family 6's snake over the four 2 x 4 quarters of the 64 x 128 wave tile
-    rdA(st, 0);
+    rdA(gated, st, 0, gp);
     rdB(st, 0);
     mm(0, 0);
     rdB(st, 1);
     mm(0, 1);
-    rdA(st, 1);
+    rdA(gated, st, 1, gp);
     mm(1, 1);
     rdB(st, 0);
     mm(1, 0);
     if constexpr (XP >= 3) {  // timing-only: the staged tiles are re-read, nothing is waited for
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      continue;
+      return;
     }
     // tile kt + 1 (issued a k-tile ago) has landed and every wave is done reading this half
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (kt + 2 < nk) dma(kt + 2, buf);
-  }
+  };
+  // two back-to-back loops, ungated tiles then gated ones: no per-tile branch in rdA
+  const int ktg = GATE ? p.gate_k0 / BK : nk;
+  for (int kt = 0; kt < ktg; ++kt) ktile(std::false_type{}, kt);
+  if constexpr (GATE)
+    for (int kt = ktg; kt < nk; ++kt) ktile(std::true_type{}, kt);
   // no DMA is in flight and every wave is past the last reads: the epilogue may use LDS
 #define WSP_GEPI(RB, RES)                                                                                   \
   switch (p.act) {                                                                                         \
@@ -783,6 +825,19 @@ bool g256_supported(const ConvGemmArgs& p) {
          (!p.sc2d || (uniform_ktiles(p) && !p.colsum && !p.lnmode && !p.row_bias));
 }
 
+// The gated A tail (AM 4): a dense 1x1 GEMM on uniform k-tiles over a uniform batch whose
+// utterances span at least a block of rows (a 256-row tile then touches at most two), no padded
+// k-tiles, a gate tail of whole 1-KB DMA pieces per utterance that fits the 32 KB behind the stages.
+bool g256_gate_supported(const ConvGemmArgs& p) {
+  if (!p.gate || !g256_supported(p) || !uniform_ktiles(p)) return false;
+  const bool dense = p.taps == 1 && p.pad == 0 && p.stride == 1 && !p.iseg && !p.seg && p.Ti == p.T;
+  const int gk = p.K - p.gate_k0;
+  return dense && p.T >= 256 && p.M % p.T == 0 && !p.colsum && !p.lnmode && !p.sc2d && p.K == p.Kp &&
+         p.gate_k0 >= 0 && p.gate_k0 % 32 == 0 && gk > 0 && gk % 128 == 0 && gk <= 4096 && p.ldg >= gk &&
+         p.ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(p.gate) & 15) == 0 &&
+         (long long)(p.M / p.T) * p.ldg * 4 < (long long)kOOB;
+}
+
 void t_g256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t s) {
   const int nwg = ((p.M + 255) / 256) * (p.N / 256);
   constexpr int lds0 = 2 * kGStage > kGEpiBytes ? 2 * kGStage : kGEpiBytes;
@@ -791,6 +846,13 @@ void t_g256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t
   // input offsets, and uniform batches with Ti == T); ragged iseg / Ti != T 1x1 GEMMs take AM 0.
   const bool dense = p.taps == 1 && p.pad == 0 && p.stride == 1 && !p.iseg && (p.seg || p.Ti == p.T);
   const int am = !uniform_ktiles(p) ? 2 : dense ? 1 : 0;
+  if (p.gate) {
+    WSP_CHECK(g256_gate_supported(p), "conv_gemm_x3: the gated A tail needs a dense 1x1 GEMM over a uniform batch");
+    const int ldsg = std::max(lds, 2 * kGStage + 2 * (p.K - p.gate_k0) * 4);  // the two gate rows behind the stages
+    hipLaunchKernelGGL((conv_gemm_g<4, false>), dim3(nwg), dim3(512), ldsg, s, p, h, l);
+    WSP_HIP(hipGetLastError());
+    return;
+  }
   if (p.sc2d) {  // conv3 + projection shortcut (check_conv_args / g256_supported: dense, uniform k-tiles)
     hipLaunchKernelGGL((conv_gemm_g<3, false>), dim3(nwg), dim3(512), lds, s, p, h, l);
     WSP_HIP(hipGetLastError());

@@ -6,6 +6,7 @@
 //           Res2 chain i=0..6: conv_k3(h1_i (+ h2_{i-1})) -> h2_i  (7 GEMMs)
 //           c3 (1x1) over cat(h2_0..6, h1_7)             -> h3   (no copy)
 //           SE: frame mean -> FC relu -> FC sigmoid -> x_{L} + h3 * g
+//           (the last block: g4 * h3 alone, or with gate_fold nothing — conv reads h3 and g4)
 //   conv    1x1 over cat(x2, x3, x4) (no copy), ReLU      -> xp   [M][1536]
 //   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
 //           -> online-softmax attentive mean/std          -> [B][3072]
@@ -192,6 +193,30 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
     run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch(g, cw, s); });
   };
 
+  // conv_cat's operands; with gate_fold its third slot is h3 of the last block with the SE gate
+  // attached (multiplied in as the A fragments are read), where the GEMM kernel takes a gate
+  ConvGemmArgs gcat{};
+  gcat.amode = kACat;
+  gcat.a[0] = x[2];
+  gcat.a[1] = x[3];
+  gcat.a[2] = x[4];
+  gcat.cseg[1] = C;
+  gcat.cseg[2] = 2 * C;
+  gcat.cseg[3] = 3 * C;
+  gcat.lda[0] = gcat.lda[1] = gcat.lda[2] = C;
+  const ConvW& wcat = cat_gate ? conv_g : conv;
+  bool fold = false;
+  if (cat_gate && gate_fold && precision == 1) {
+    ConvGemmArgs g = gcat;
+    g.a[2] = h3;
+    g.gate = W.gate;
+    g.ldg = C;
+    g.gate_k0 = 2 * C;
+    fill(g, wcat, M, T, 1, 0, xp, 1536, kActRelu, nullptr, true, seg, B);
+    fold = conv_gemm_x3_gate_ok(g, x3_variant);
+    if (fold) gcat = g;
+  }
+
   gemm("layer1", layer1, feats, feat_dim, x[1], C, M, T, 1, 2, kActRelu, s, seg, B);
   for (int li = 0; li < 3; ++li) {
     const Block& b = blk[li];
@@ -247,21 +272,15 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
       else launch_frame_stats(h3, C, B, T, C, W.gmean, C, 0, 0, s, seg);
       launch_small_linear({W.gmean, C, b.se1.wt, b.se1.bias, W.ghid, 128, B, C, 128, 1}, s);
       launch_small_linear({W.ghid, 128, b.se2.wt, b.se2.bias, W.gate, C, B, 128, C, 3}, s);
-      // cat_gate: the last block stores only g4 * h3 (conv_cat adds out3 through its weights)
+    });
+    // cat_gate: the last block stores only g4 * h3 (conv_cat adds out3 through its weights);
+    // gate_fold: not even that — conv_cat reads h3 and the gate (x[4] stays unwritten)
+    if (li == 2 && fold) continue;
+    run("se.scale", 0, s, [&] {
       launch_residual_scale(cat_gate && li == 2 ? nullptr : xin, h3, W.gate, x[li + 2], B, T, C, s, seg, M);
     });
   }
-  {
-    ConvGemmArgs g{};
-    g.amode = kACat;
-    g.a[0] = x[2];
-    g.a[1] = x[3];
-    g.a[2] = x[4];
-    g.cseg[1] = C;
-    g.cseg[2] = 2 * C;
-    g.cseg[3] = 3 * C;
-    gemm3("conv_cat", g, cat_gate ? conv_g : conv, 1, 0, xp, 1536);
-  }
+  gemm3("conv_cat", gcat, wcat, 1, 0, xp, 1536);
   if (glob) {
     run("glob_ctx", 0, s, [&] {
       launch_frame_stats(xp, 1536, B, T, 1536, W.gstats, 3072, 1, 1536, s, seg);

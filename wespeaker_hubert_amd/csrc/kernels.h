@@ -86,6 +86,14 @@ struct ConvGemmArgs {
   const float* ln_g;
   const float* ln_b;
   float ln_eps;
+  // Gated tail of A (x3 tile family 7, dense 1x1 GEMMs over uniform batches with T >= 256 and
+  // K == Kp; conv_gemm_x3_t6.hip): A(m, k) is multiplied by gate[m / T][k - gate_k0] for
+  // k >= gate_k0 (a multiple of 32) before the bf16 hi / lo split — the SE gate of ECAPA's last
+  // block folded into conv_cat.  gate = [M / T][ldg] fp32, K - gate_k0 a multiple of 128 and at
+  // most 4096; null = no gate.  conv_gemm_x3_gate_ok() tells whether a launch takes it; every
+  // other kernel refuses a non-null gate.
+  const float* gate;
+  int ldg, gate_k0;
 };
 
 // Fills the 1-D defaults (stride 1, Ti = T) of a zero-initialised ConvGemmArgs.
@@ -110,6 +118,8 @@ void launch_colsum_mean(const double* part, int block_rows, int T, int B, int N,
                         hipStream_t s);
 void launch_conv_gemm_x3(const ConvGemmArgs& p, const void* whi, const void* wlo, int variant,
                          hipStream_t s);
+// whether launch_conv_gemm_x3(p, ., ., variant) takes p.gate (p filled as for the launch)
+bool conv_gemm_x3_gate_ok(const ConvGemmArgs& p, int variant);
 
 
 // tile: 0 = 128x128 block (N % 128 == 0), 1 = 128x64 block (N % 64 == 0)

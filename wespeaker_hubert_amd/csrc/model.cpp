@@ -374,6 +374,7 @@ const Opt kOpts[] = {
     {"in_planes", &I::m_ch, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
     {"res2_fused", &I::res2_fused, 0, 1, kNoHole, "res2_fused must be 0 or 1"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
+    {"gate_fold", &I::gate_fold, 0, 1, kNoHole, "gate_fold must be 0 or 1"},
     {"res_prefetch", &I::res_prefetch, 0, 1, kNoHole, "res_prefetch must be 0 or 1"},
     {"res_tail", &I::res_tail, 0, 2, kNoHole, "res_tail must be 0 (off), 1 (tail + next conv1) or 2 (tail alone)"},
     {"sc_fuse", &I::sc_fuse, 0, 3, kNoHole, "sc_fuse must be 0 .. 3 (bit 0: one GEMM, bit 1: in the tail)"},

@@ -163,6 +163,11 @@ struct Model::Impl {
   // writes only g4 * h3_4 (no residual read) (option "cat_gate", default on)
   ConvW conv_g;
   int cat_gate = 1;
+  // with cat_gate: the gate pass itself is folded into conv_cat, whose third A segment is h3_4
+  // multiplied by g4 as its fragments are read (ConvGemmArgs::gate) — no g4 * h3_4 tensor is
+  // written or read.  Effective where the GEMM takes a gate (bf16x3 tile family 7 on uniform
+  // batches with T >= 256); everything else keeps the gate pass (option "gate_fold", default on)
+  int gate_fold = 1;
   void* pool2_frag = nullptr;  // pool.linear2 in MFMA B-fragment order for astp_fused.hip
   // 0: linear2 GEMM + separate pooling kernel; 1: astp_fused.hip (option "astp_fused"; 256 channels
   // per block, att chunks two ahead in an LDS-DMA ring, W2 in VGPRs: C2 0.465 -> 0.31 ms)

@@ -129,7 +129,9 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
 
 /* ------------------------------------------------------------- model --- */
 /* arch: "ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
- * "ECAPA_TDNN_GLOB_c1024", "ResNet18/34/50/101/152/221/293"
+ * "ECAPA_TDNN_GLOB_c1024", "ResNet18/34/50/101/152/221/293",
+ * "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP", "CAMPPlus" (CAM++: feat_dim a
+ * multiple of 8, TSTP pooling, no emb_bn / two_emb_layer, >= 3 frames)
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
  * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
  * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /
@@ -211,6 +213,9 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *                  splits its A fragments (default; bit-identical to 0).  Effective at precision 1,
  *                  x3_variant 7 on uniform batches of T >= 256 frames; ragged or shorter batches
  *                  and the other kernels keep the gate pass.  0 = the gate pass throughout
+ *   "cam_fused"    CAMPPlus: 1 (default) = the dense layers' BatchNorm + ReLU inside the 1x1
+ *                  GEMM's A prologue; 0 = an elementwise pass of its own into scratch (A/B
+ *                  runs only; bit-identical)
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block

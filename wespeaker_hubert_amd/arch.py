@@ -37,6 +37,12 @@ SIMAM_ARCHS = {
     "SimAM_ResNet100_ASP": (6, 16, 24, 3),
 }
 
+CAMPP_ARCHS = {
+    # name: (dense layers, dilation) per block — campplus.py:333-380 (kernel 3, growth 32, bn_size 4)
+    "CAMPPlus": ((12, 24, 16), (1, 2, 2)),
+}
+CAMPP_SEG = 100  # CAMLayer.seg_pooling's segment length
+
 
 @dataclass
 class ModelSpec:
@@ -57,6 +63,8 @@ class ModelSpec:
             return "resnet"
         if self.arch.startswith("SimAM_ResNet"):
             return "simam"
+        if self.arch in CAMPP_ARCHS:
+            return "campplus"
         raise KeyError(self.arch)
 
 
@@ -65,10 +73,25 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
 
     Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57).
     """
-    if arch not in ECAPA_ARCHS and arch not in RESNET_ARCHS and arch not in SIMAM_ARCHS:
+    if arch not in ECAPA_ARCHS and arch not in RESNET_ARCHS and arch not in SIMAM_ARCHS and arch not in CAMPP_ARCHS:
         raise KeyError(f"{arch} not found !!! (supported: "
-                       f"{sorted(ECAPA_ARCHS) + sorted(RESNET_ARCHS) + sorted(SIMAM_ARCHS)})")
+                       f"{sorted(ECAPA_ARCHS) + sorted(RESNET_ARCHS) + sorted(SIMAM_ARCHS) + sorted(CAMPP_ARCHS)})")
     kw = dict(model_args)
+    if arch in CAMPP_ARCHS:
+        # CAMPPlus(feat_dim=80, embed_dim=512, pooling_func='TSTP', growth_rate=32, bn_size=4,
+        #          init_channels=128, config_str='batchnorm-relu')
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 512)),
+                         pooling_func=kw.pop("pooling_func", "TSTP"))
+        if spec.pooling_func != "TSTP":
+            raise NotImplementedError("CAMPPlus path implements TSTP pooling (the hub configuration)")
+        if spec.feat_dim < 8 or spec.feat_dim % 8:
+            raise ValueError("CAMPPlus feat_dim must be a positive multiple of 8")
+        for key, want in (("growth_rate", 32), ("bn_size", 4), ("init_channels", 128),
+                          ("config_str", "batchnorm-relu")):
+            if kw.pop(key, want) != want:
+                raise NotImplementedError(f"CAMPPlus path implements {key}={want!r} (the hub configuration)")
+        spec.extra = kw
+        return spec
     if arch in SIMAM_ARCHS:
         # SimAM_ResNet*_ASP(in_planes=64, embed_dim=256, acoustic_dim=80, dropout=0)
         spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("acoustic_dim", 80)),
@@ -177,7 +200,46 @@ def simam_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def campplus_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of CAMPPlus (campplus.py:245-396): FCM head, xvector.* dense TDNN."""
+    layers, _ = CAMPP_ARCHS[spec.arch]
+    out: ParamList = [("head.conv1.weight", (32, 1, 3, 3))] + _bn("head.bn1", 32)
+    for stage in (1, 2):
+        for bi in (0, 1):
+            p = f"head.layer{stage}.{bi}"
+            out += [(p + ".conv1.weight", (32, 32, 3, 3))] + _bn(p + ".bn1", 32)
+            out += [(p + ".conv2.weight", (32, 32, 3, 3))] + _bn(p + ".bn2", 32)
+            if bi == 0:
+                out += [(p + ".shortcut.0.weight", (32, 32, 1, 1))] + _bn(p + ".shortcut.1", 32)
+    out += [("head.conv2.weight", (32, 32, 3, 3))] + _bn("head.bn2", 32)
+    out += [("xvector.tdnn.linear.weight", (128, 32 * (spec.feat_dim // 8), 5))]
+    out += _bn("xvector.tdnn.nonlinear.batchnorm", 128)
+    ch = 128
+    for b, n in enumerate(layers):
+        for i in range(n):
+            p = f"xvector.block{b + 1}.tdnnd{i + 1}"
+            cin = ch + 32 * i
+            out += _bn(p + ".nonlinear1.batchnorm", cin)
+            out += [(p + ".linear1.weight", (128, cin, 1))]
+            out += _bn(p + ".nonlinear2.batchnorm", 128)
+            out += [(p + ".cam_layer.linear_local.weight", (32, 128, 3)),
+                    (p + ".cam_layer.linear1.weight", (64, 128, 1)), (p + ".cam_layer.linear1.bias", (64,)),
+                    (p + ".cam_layer.linear2.weight", (32, 64, 1)), (p + ".cam_layer.linear2.bias", (32,))]
+        ch += 32 * n
+        t = f"xvector.transit{b + 1}"
+        out += _bn(t + ".nonlinear.batchnorm", ch) + [(t + ".linear.weight", (ch // 2, ch, 1))]
+        ch //= 2
+    out += _bn("xvector.out_nonlinear.batchnorm", ch)
+    out += [("xvector.dense.linear.weight", (spec.embed_dim, 2 * ch, 1)),
+            ("xvector.dense.nonlinear.batchnorm.running_mean", (spec.embed_dim,)),
+            ("xvector.dense.nonlinear.batchnorm.running_var", (spec.embed_dim,)),
+            ("xvector.dense.nonlinear.batchnorm.num_batches_tracked", ())]
+    return out
+
+
 def param_list(spec: ModelSpec) -> ParamList:
+    if spec.family == "campplus":
+        return campplus_params(spec)
     if spec.family == "ecapa":
         return ecapa_params(spec)
     if spec.family == "simam":
@@ -201,6 +263,32 @@ def simam_gflop_per_utt(spec: ModelSpec, T: int) -> float:
             F, t, cin = Fo, To, planes
     cf = cin * F
     macs += t * (cf * 128 * 2) + 2 * cf * spec.embed_dim
+    return 2.0 * macs / 1e9
+
+
+def campplus_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one CAMPPlus forward over T frames: FCM head, strided TDNN,
+    the dense layers (1x1 conv, k3 local conv, mask linears per segment), transits, embedding."""
+    layers, _ = CAMPP_ARCHS[spec.arch]
+    F = spec.feat_dim
+    macs = F * T * 32 * 9  # stem
+    for _ in (1, 2):
+        F //= 2
+        macs += F * T * 32 * (288 + 32 + 288)  # strided block: conv1, shortcut, conv2
+        macs += F * T * 32 * (288 + 288)       # plain block
+    F //= 2
+    macs += F * T * 32 * 288                   # head.conv2
+    t = (T - 1) // 2 + 1
+    nseg = (t + CAMPP_SEG - 1) // CAMPP_SEG
+    macs += t * 128 * 32 * F * 5               # xvector.tdnn
+    ch = 128
+    for n in layers:
+        for i in range(n):
+            macs += t * 128 * (ch + 32 * i) + t * 32 * 384 + nseg * (128 * 64 + 64 * 32)
+        ch += 32 * n
+        macs += t * ch * (ch // 2)
+        ch //= 2
+    macs += 2 * ch * spec.embed_dim
     return 2.0 * macs / 1e9
 
 

@@ -2,7 +2,7 @@
 // (reference state_dict order), pack-and-upload helpers (BatchNorm folding and packing run on
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
 // The families' tables, folds, workspace layouts and forward schedules are in ecapa_model.cpp,
-// resnet_model.cpp (ResNet and SimAM-ResNet) and hubert_model.cpp.
+// resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp and campplus_model.cpp.
 #include "model_impl.h"
 
 namespace wsp {
@@ -232,6 +232,15 @@ void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool em
     m.x3_variant = 7;  // every GEMM whose operands family 7 takes (r4), the rest on 6
     m.streams = 2;  // HuBERT + ECAPA C4 chain +2.6 %
     m.build_hubert_params();
+  } else if (arch == "CAMPPlus") {
+    // campplus.py:333-413: FCM head + dense TDNN, TSTP, embedding without an affine BatchNorm tail
+    WSP_CHECK(!two_emb && !emb_bn, "CAMPPlus has no emb_bn / two_emb_layer");
+    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "CAMPPlus feat_dim must be a positive multiple of 8");
+    WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
+    m.ecapa = false;
+    m.campp = true;
+    m.x3_variant = 4;  // xvector.tdnn is the one implicit GEMM (N = 128)
+    m.build_campp_params();
   } else {
     throw InvalidArg{"unsupported arch " + arch};
   }
@@ -271,6 +280,8 @@ void Model::finalize() {
     m.finalize_simam();
   else if (m.hubert)
     m.finalize_hubert();
+  else if (m.campp)
+    m.finalize_campp();
   else
     m.finalize_resnet();
   for (auto& p : m.params) std::vector<float>().swap(p.host);
@@ -283,7 +294,9 @@ int Model::feat_dim() const { return impl->feat_dim; }
 // workspace of one sub-batch of B utterances, 256-byte granules
 size_t Model::Impl::ws_bytes_one(int B, int T) const {
   const int bc = ecapa ? ecapa_chunk(B, T) : B;
-  const size_t f = ecapa ? ecapa_ws_floats(bc, (size_t)bc * T) : resnet_ws_floats(B, T);
+  const size_t f = ecapa   ? ecapa_ws_floats(bc, (size_t)bc * T)
+                   : campp ? campp_ws_floats(B, T)
+                           : resnet_ws_floats(B, T);
   return (f * sizeof(float) + 255) & ~size_t(255);
 }
 
@@ -305,6 +318,7 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
   WSP_CHECK(ws_bytes >= workspace_bytes(B, T), "workspace too small");
   WSP_CHECK(m.ecapa || m.precision == 1, "ResNet runs on the bf16x3 kernels only (precision=1)");
   WSP_CHECK(!m.simam || (T + 7) / 8 >= 2, "SimAM-ResNet needs >= 2 frames after the three stride-2 stages");
+  WSP_CHECK(!m.campp || T >= 3, "CAMPPlus needs >= 3 frames (2 after the stride-2 TDNN)");
   char* wsb = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
   const int ns = m.nsub(B);
   if (ns > 1) m.fork(s, ns);
@@ -322,6 +336,8 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
                         si);
     } else if (m.simam)
       m.forward_simam(f, nb, T, e, wsf, si);
+    else if (m.campp)
+      m.forward_campp(f, nb, T, e, wsf, si);
     else
       m.forward_resnet(f, nb, T, e, wsf, si);
     wsb += m.ws_bytes_one(nb, T);
@@ -373,6 +389,7 @@ const Opt kOpts[] = {
     {"layer", &I::h_layer_sel, -1, 12, kNoHole, "layer must be -1 (weighted sum) or 0..12"},
     {"in_planes", &I::m_ch, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
     {"res2_fused", &I::res2_fused, 0, 1, kNoHole, "res2_fused must be 0 or 1"},
+    {"cam_fused", &I::cam_fused, 0, 1, kNoHole, "cam_fused must be 0 (separate BN-ReLU pass) or 1 (GEMM prologue)"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
     {"gate_fold", &I::gate_fold, 0, 1, kNoHole, "gate_fold must be 0 or 1"},
     {"res_prefetch", &I::res_prefetch, 0, 1, kNoHole, "res_prefetch must be 0 or 1"},

@@ -4,6 +4,7 @@
 //   ecapa_model.cpp   ECAPA-TDNN
 //   resnet_model.cpp  ResNet and SimAM-ResNet
 //   hubert_model.cpp  HuBERT / WavLM front end
+//   campplus_model.cpp  CAM++
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -296,6 +297,41 @@ struct Model::Impl {
   HubertPlan hubert_plan(int B, const int* lens) const;
   size_t hubert_ws_floats(const HubertPlan& pl) const;
   void forward_hubert(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws, hipStream_t s);
+
+  // ------------------------------------------------------------------ CAM++ (campplus_model.cpp) --
+  // FCM head NHWC [B][F][T][32] (stem_w / stem_b as the ResNets'), then frame rows [B][T'][C]
+  bool campp = false;
+  struct FcmBlock {
+    bool strided = false;  // first block of a stage: conv1 and the projection shortcut stride (2, 1)
+    // BN-folded weights and biases: conv1 as fcm_conv.hip fragments when strided, else as
+    // conv3x3_img.hip fragments like conv2; the shortcut as fcm_conv.hip fragments
+    void *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;
+    float *b1 = nullptr, *b2 = nullptr, *bsc = nullptr;
+  } fcm_blk[4];
+  void* fcm_out_w = nullptr;  // head.conv2 + bn2
+  float* fcm_out_b = nullptr;
+  ConvW cam_tdnn;
+  struct CamLayer {
+    int cin = 0;
+    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;  // nonlinear1 / nonlinear2 as affines
+    void *w1 = nullptr, *wl = nullptr;  // linear1 / linear_local as cam_pack_b fragments
+    LinW l1, l2;                        // the context mask's two linears
+  };
+  struct CamBlock {
+    std::vector<CamLayer> layers;
+    float *ts = nullptr, *tt = nullptr;  // transit BatchNorm
+    void* tw = nullptr;
+  } cam_blk[3];
+  float *cam_out_s = nullptr, *cam_out_t = nullptr;  // out_nonlinear
+  LinW cam_head;  // dense with its affine-free BatchNorm folded in
+  // 1 = the dense layers' BN-ReLU inside the GEMM's A prologue; 0 = an elementwise pass of its own
+  // into scratch (A/B runs only; option "cam_fused")
+  int cam_fused = 1;
+  void build_campp_params();
+  void finalize_campp();
+  int campp_chunk(int B, int T) const;
+  size_t campp_ws_floats(int B, int T) const;
+  void forward_campp(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s);
 
   // ------------------------------------------------------------------- shared (model.cpp) --
   // 1 = bf16x3 split MFMA (default), 0 = exact f32 MFMA

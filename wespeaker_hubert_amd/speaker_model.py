@@ -184,7 +184,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -258,9 +258,9 @@ class HipSpeakerModel(_HipHandle):
         return self.spec.family == "ecapa"
 
     def __call__(self, feats: torch.Tensor):
-        # SimAM_ResNet*_ASP.forward returns the embedding itself (samresnet.py:135-143);
-        # ECAPA / ResNet return (aux, embed)
-        if self.spec.family == "simam":
+        # SimAM_ResNet*_ASP.forward and CAMPPlus.forward return the embedding itself
+        # (samresnet.py:135-143, campplus.py:409-413); ECAPA / ResNet return (aux, embed)
+        if self.spec.family in ("simam", "campplus"):
             return self.embed(feats)
         return None, self.embed(feats)
 

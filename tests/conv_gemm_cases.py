@@ -279,6 +279,20 @@ def group14():
             make_case(name="g14 W exact", a=[a], w=to_bf16(w), M=B * T, T=T, bias=bias, prod_exp=17)]
 
 
+def group15():
+    """The prefetched-residual epilogue (role = 2 with a residual on the tiles of at most four
+    accumulator tiles per wave: the residual is loaded ahead of the last two k-tiles).  M = 130
+    leaves the last 128-row block partial; with K = 64 the k-loop ahead of the prefetch runs zero
+    times, with K = 192 twice.  The wide tiles, family 7 and the f32 kernel ignore `role`."""
+    g, out = _Gen(115), []
+    B, T = 2, 65
+    for K in (64, 192):
+        for N in (32, 64, 128, 256):
+            out.append(make_case(name=f"g15 K={K} N={N}", a=[g.a(B * T, K)], w=g.w(N, K, 1), M=B * T, T=T, role=2,
+                                 bias=g.vec(N), res=g.a(B * T, N + 8), act=ACT_RELU))
+    return out
+
+
 def f32_takes(c):
     """Operands launch_conv_gemm documents: 1-D convs with N % 64 == 0, no column sums."""
     return (not c["conv2d"] and not c["sc2d"] and not c["lnmode"] and c["N"] % 64 == 0 and not c["colsum"]

@@ -287,3 +287,7 @@ def test_group13_epilogue_matrix(tmp_path):
 def test_group14_split_term_probes(tmp_path):
     _simple(tmp_path, "group 14", cases.group14(), {"128x128", "256x128", "256x256", "256x256mf16", "g256",
                                                     "f32_128x128"})
+
+
+def test_group15_prefetched_residual(tmp_path):
+    _simple(tmp_path, "group 15", cases.group15(), ALL_X3 | {"f32_128x128", "f32_128x64"})

@@ -2,21 +2,15 @@
 // families 6 (conv_gemm_x3_t5.hip, register-staged) and 7 (conv_gemm_x3_t6.hip, LDS-DMA) on the
 // operand shapes the models launch, plus the operand forms only tests reach (ragged row bias,
 // 1x1 with Ti != T).  Family 7 must equal family 6 bit for bit (outputs and SE column sums); then
-// interleaved timing rounds.  (r5's family 8, a ping-pong k-loop, and family 9, family 7 on 16 waves
-// of 64 x 64 or 8 waves of 32 x 256, and a persistent family 7, were measured with this tool and
-// pruned: profiles/r5a_gemm_check.txt, r5m_gemm_family9.txt, r5p_gemm_persistent.txt; a staggered
-// start of every other CU's first block, r5ac_gemm_stagger_experiment.txt.)
-//   gemm_check [case|all] [reps] [variants, e.g. 67]
+// interleaved timing rounds.  The tool links against libwsp_hip.so and calls the tile launchers
+// the library exports, so what it compares are the shipped kernels; only the fill / split / diff
+// helpers below are its own.  (Families 8 - 10 and the r5 / r6 k-loop experiments were measured
+// with earlier forms of this tool and pruned: DESIGN.md, "r3 / r5 / r6 pruning".)
+//   gemm_check [case|all] [reps] [variants: 6, 7 or 67]
 // Case gate_seg (by name only; not part of "all"): family 7's gated instance (AM 4: the third A
 // segment multiplied by a per-utterance gate as its fragments are read) against residual_scale<false>
 // followed by the ungated instance, bit for bit, on 3 utterances of 300 frames (a tile straddling
 // two utterances, a partial last tile).
-// r6 experiment variants: 8 = family 7 with the A split replaced by a bit reinterpretation
-// (timing only: no split VALU, same LDS / DMA traffic; its outputs differ), 9 = family 7 with the
-// next tile's DMA pieces interleaved into the k-tile's quarters (bit-identical); 10 = family 7's
-// LDS -> split -> MFMA loop alone (no DMA, no barrier in the k-loop; timing only); 11 = 10 without
-// the split (LDS -> MFMA alone; timing only); 'c' (12) = family 10 (W fragments from L2 into
-// registers, A alone through a 4-deep LDS ring; bit-identical to 6 / 7).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -24,13 +18,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#define WSP_G7_XP 1
-#include "../wespeaker_hubert_amd/csrc/conv_gemm_x3_t5.hip"
-#include "../wespeaker_hubert_amd/csrc/conv_gemm_x3_t6.hip"
-#include "../wespeaker_hubert_amd/csrc/ops.hip"  // residual_scale_kernel<false>: the gate pass of case gate_seg
-namespace wsp { namespace x3 {
-void t_4x2_2x4_sw1(const ConvGemmArgs&, const __bf16*, const __bf16*, hipStream_t) { std::abort(); }
-} }
+#include "../wespeaker_hubert_amd/csrc/conv_gemm_x3_impl.h"  // x3:: tile launchers (declarations), check_conv_args
 using namespace wsp;
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); std::exit(1); } } while (0)
@@ -168,8 +156,6 @@ void run(const Case& c, int v, float* out, double* cs, hipStream_t s) {
   q.out = out;
   q.colsum = cs;
   if (v == 6) x3::t_4x2_2x4_mf16(q, c.whi, c.wlo, s);
-  else if (v == 12) x3::t_gb256(q, c.whi, c.wlo, s);  // family 10 ('c')
-  else if (v >= 8) x3::t_g256_xp(q, c.whi, c.wlo, s, v == 8 ? 1 : v == 9 ? 2 : v - 7);  // r6 experiments
   else {
     if (!x3::g256_supported(q)) { std::fprintf(stderr, "%s: family %d does not take these operands\n", c.name.c_str(), v); std::exit(2); }
     x3::t_g256(q, c.whi, c.wlo, s);
@@ -182,7 +168,10 @@ int main(int argc, char** argv) {
   const int reps = argc > 2 ? std::atoi(argv[2]) : 10;
   const std::string vs = argc > 3 ? argv[3] : "67";
   std::vector<int> vars;
-  for (char ch : vs) vars.push_back(ch >= 'a' ? ch - 'a' + 10 : ch - '0');  // 'a' = 10, 'b' = 11
+  for (char ch : vs) {
+    if (ch != '6' && ch != '7') { std::fprintf(stderr, "gemm_check: variants are 6 and 7\n"); return 2; }
+    vars.push_back(ch - '0');
+  }
   const std::vector<int> ragged = {300, 257, 511, 123, 800, 6};
   std::vector<Case> cases;
   auto want = [&](const char* n) { return which == "all" || which == n; };
@@ -237,29 +226,25 @@ int main(int argc, char** argv) {
     return d ? 1 : 0;
   }
   for (const Case& c : cases) {
-    std::vector<float*> out(13, nullptr);
-    std::vector<double*> cs(13, nullptr);
-    std::vector<int> vv;  // family 10 takes uniform-k-tile operands only (gb256_supported)
-    for (int v : vars)
-      if (v != 12 || x3::gb256_supported(c.g)) vv.push_back(v);
-      else std::printf("%-10s family 12 skipped: operands family 10 does not take\n", c.name.c_str());
-    for (int v : vv) {
+    std::vector<float*> out(8, nullptr);
+    std::vector<double*> cs(8, nullptr);
+    for (int v : vars) {
       CK(hipMalloc(&out[v], c.out_words * 4));
       CK(hipMemset(out[v], 0xff, c.out_words * 4));
       if (c.cs_words) CK(hipMalloc(&cs[v], c.cs_words * 4));
       run(c, v, out[v], cs[v], s);
     }
     CK(hipStreamSynchronize(s));
-    for (int v : vv) {
-      if (v == vv[0]) continue;
-      const unsigned long long d = ndiff(out[vv[0]], out[v], c.out_words);
-      const unsigned long long dc = c.cs_words ? ndiff(cs[vv[0]], cs[v], c.cs_words) : 0;
+    for (int v : vars) {
+      if (v == vars[0]) continue;
+      const unsigned long long d = ndiff(out[vars[0]], out[v], c.out_words);
+      const unsigned long long dc = c.cs_words ? ndiff(cs[vars[0]], cs[v], c.cs_words) : 0;
       std::printf("%-10s family %d vs %d: %llu of %zu outputs differ, %llu column-sum words differ\n", c.name.c_str(), v,
-                  vv[0], d, c.out_words, dc);
-      bad += (d != 0 || dc != 0) && v != 8 && v != 10 && v != 11;  // variants 8, 10, 11 are timing-only
+                  vars[0], d, c.out_words, dc);
+      bad += d != 0 || dc != 0;
     }
     for (int round = 0; round < 3; ++round)
-      for (int v : vv) {
+      for (int v : vars) {
         CK(hipEventRecord(e0, s));
         for (int r = 0; r < reps; ++r) run(c, v, out[v], cs[v], s);
         CK(hipEventRecord(e1, s));
@@ -271,7 +256,7 @@ int main(int argc, char** argv) {
                     v, c.g.M, c.g.N, c.g.K, ms, c.flops / (ms * 1e-3) / 1e12, 3 * c.flops / (ms * 1e-3) / 1e12);
         std::fflush(stdout);
       }
-    for (int v : vv) {
+    for (int v : vars) {
       CK(hipFree(out[v]));
       if (cs[v]) CK(hipFree(cs[v]));
     }

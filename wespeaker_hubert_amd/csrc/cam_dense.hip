@@ -13,6 +13,7 @@
 // consecutive k 8 (l >> 4) .. + 7; accumulator register r is row 4 (l >> 4) + r, column l & 15.
 #include "cam_dense.h"
 
+#include "bf16x3.h"
 #include "gemm_common.h"
 #include "pack.h"
 
@@ -37,16 +38,6 @@ std::vector<uint16_t> cam_pack_b(const float* w, int N, int K, int ldw) {
 }
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = (__bf16)v[e];
-    l[e] = (__bf16)(v[e] - (float)h[e]);
-  }
-}
 
 __device__ __forceinline__ void store1(__amdgpu_buffer_rsrc_t r, float y, int off) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), r, off, 0, 0);
@@ -122,7 +113,7 @@ __global__ __launch_bounds__(256) void cam_gemm_kernel(const CamGemmArgs p) {
         const float a = araw[i][e >> 2][e & 3];
         v[e] = p.s1 ? fmaxf(fmaf(a, sraw[e >> 2][e & 3], traw[e >> 2][e & 3]), 0.f) : a;
       }
-      split8(v, ah[i], al[i]);
+      split(v, ah[i], al[i]);
     }
   };
 
@@ -144,12 +135,7 @@ __global__ __launch_bounds__(256) void cam_gemm_kernel(const CamGemmArgs p) {
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(w + (j * 64 + lane) * 16);
       const bf16x8 bl = *reinterpret_cast<const bf16x8*>(w + (512 + j * 64 + lane) * 16);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        f32x4& c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, c, 0, 0, 0);
-      }
+      for (int i = 0; i < 2; ++i) mma3(ah[i], al[i], bh, bl, acc[i][j]);
     }
     // the other buffer was last read in step ks - 1, which every wave left at the barrier below
     if (more) stage((ks + 1) & 1);
@@ -275,19 +261,14 @@ __global__ __launch_bounds__(256) void cam_local_kernel(const CamLocalArgs p) {
       const int off = ok ? ((am[i] + d) * p.ldh + c0) * 4 : kOOB;
       const f32x4 v0 = bload4(rh, off), v1 = bload4(rh, ok ? off + 16 : kOOB);
       const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      split8(v, ah[i], al[i]);
+      split(v, ah[i], al[i]);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const bf16x8 bh = __builtin_bit_cast(bf16x8, wsrc[((ks * 2 + 0) * 2 + j) * 64 + lane]);
       const bf16x8 bl = __builtin_bit_cast(bf16x8, wsrc[((ks * 2 + 1) * 2 + j) * 64 + lane]);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        f32x4& c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, c, 0, 0, 0);
-      }
+      for (int i = 0; i < 2; ++i) mma3(ah[i], al[i], bh, bl, acc[i][j]);
     }
   }
   const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.out);

@@ -308,12 +308,7 @@ __device__ __forceinline__ void g_epilogue_cs(const ConvGemmArgs& p, f32x4 (&acc
   }
 }
 
-// XP: development experiments (tools/gemm_check built with -DWSP_G7_XP; the library instantiates
-// XP = 0 only): 1 = timing-only, the A fragments bit-reinterpreted instead of split (no split
-// VALU; wrong results); 2 = the next tile's DMA pieces interleaved into the quarters; 3 = timing-
-// only, no DMA and no barrier inside the k-loop (every k-tile re-reads the two staged tiles: the
-// LDS -> split -> MFMA loop alone); 4 = 3 without the split (LDS -> MFMA alone)
-template <int AM, bool CSK, int LNM = 0, int XP = 0>
+template <int AM, bool CSK, int LNM = 0>
 __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, const __bf16* __restrict__ whi,
                                                       const __bf16* __restrict__ wlo) {
   using L = Lds<true, 16>;
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   // residual_scale_kernel<false> stored it: same split, same MFMA order, bit-identical results)
   constexpr bool DENSE = AM == 1 || AM == 3 || AM == 4;
   constexpr bool GATE = AM == 4;
-  static_assert(!GATE || (!CSK && LNM == 0 && XP == 0), "the gated instance: plain epilogues only");
+  static_assert(!GATE || (!CSK && LNM == 0), "the gated instance: plain epilogues only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -381,7 +376,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   const __amdgpu_buffer_rsrc_t rwl = make_rsrc(wlo);
   const int nk = p.Kp / BK;  // >= 2 (Kp % 64 == 0)
   int jt = 0, ct = 0;  // tap and channel of the next k-tile to fetch (k-tiles are fetched in order)
-  auto dma = [&](int kt, int buf, int part = 3) {  // part bit 0: A pieces, bit 1: W pieces
+  auto dma = [&](int kt, int buf) {
     unsigned char* st = smem + buf * kGStage;
     const int off = jt * p.dil - p.pad;
     const float* base = p.a[0];
@@ -398,7 +393,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
     const __amdgpu_buffer_rsrc_t ra = make_rsrc(base);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if (!(part & 1)) break;
       if constexpr (DENSE) {
         const int ar = AM == 3 && ct >= p.cseg[1] ? a_s[i] : a_r[i];
         g_dma(ra, st + (4 * wave + i) * 1024, ar >= 0 ? (ar * ld + cl + (i & 1 ? ac1 : ac0)) * 4 : kOOB);
@@ -417,12 +411,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      if (!(part & 2)) break;
       const int o = woff[i] + kt * 64;
       g_dma(rwh, st + kGA + (2 * wave + i) * 1024, o);
       g_dma(rwl, st + kGA + kGW + (2 * wave + i) * 1024, o);
     }
-    if (!(part & 2)) return;  // the tap / channel cursor advances with the W half (issued last)
     ct += 32;
     if (ct >= p.cin) {
       ct -= p.cin;
@@ -455,11 +447,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
         const unsigned char* gr = gp + (r >= g_nb ? g_slot : 0);
         x0 = x0 * *reinterpret_cast<const f32x4*>(gr);
         x1 = x1 * *reinterpret_cast<const f32x4*>(gr + 16);
-      }
-      if constexpr (XP == 1 || XP == 4) {
-        ah[i] = __builtin_bit_cast(bf16x8, x0);
-        al[i] = __builtin_bit_cast(bf16x8, x1);
-        continue;
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -514,37 +501,12 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   dma(1, 1);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile 0 landed (8 DMAs per k-tile and lane)
   __builtin_amdgcn_s_barrier();
-  // (XP 2 keeps this prologue: tile 1 is in flight, iteration 0 issues nothing, iteration kt >= 1
-  // issues tile kt + 1 into the buffer tile kt - 1 left)
   auto ktile = [&](auto gated, int kt) {
     const int buf = kt & 1;
     const unsigned char* st = smem + buf * kGStage;
     // gated tiles: the lane's gate chunks 2 qk, 2 qk + 1 of this k-tile (slot 0)
     const unsigned char* gp =
         decltype(gated)::value ? smem + 2 * kGStage + (kt * BK - p.gate_k0 + 8 * qk) * 4 : nullptr;
-    if constexpr (XP == 2) {
-      // the next tile's pieces go out between this tile's quarters (the other buffer is free:
-      // every wave passed the barrier that ended tile kt - 1's reads of it)
-      rdA(gated, st, 0);
-      rdB(st, 0);
-      mm(0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (kt >= 1 && kt + 1 < nk) dma(kt + 1, buf ^ 1, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      rdB(st, 1);
-      mm(0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (kt >= 1 && kt + 1 < nk) dma(kt + 1, buf ^ 1, 2);
-      __builtin_amdgcn_sched_barrier(0);
-      rdA(gated, st, 1);
-      mm(1, 1);
-      rdB(st, 0);
-      mm(1, 0);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      return;
-    }
     // family 6's snake over the four 2 x 4 quarters of the 64 x 128 wave tile
     rdA(gated, st, 0, gp);
     rdB(st, 0);
@@ -555,10 +517,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
     mm(1, 1);
     rdB(st, 0);
     mm(1, 0);
-    if constexpr (XP >= 3) {  // timing-only: the staged tiles are re-read, nothing is waited for
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      return;
-    }
     // tile kt + 1 (issued a k-tile ago) has landed and every wave is done reading this half
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -601,215 +559,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   }
 #undef WSP_GEPI
 }
-
-#ifdef WSP_G7_XP
-// ---------------------------------------------------------------------------------------------
-// Tile family 10 (r6): family 7's 256 x 256 tile, waves and epilogue, with W's fragments loaded
-// by each wave straight from L2 into registers (16 B per lane: the [N][Kp] hi / lo images already
-// hold a 16x16x32 B fragment's 8 k of one column contiguously) and only A staged through LDS, in a
-// 4-deep ring of 32 KB stages (family 7: A + W in a 2-deep ring of 64 KB).  Per k-tile a wave
-// reads 8 A fragments from LDS (family 7: 24 fragment reads), issues 4 A DMA pieces (family 7: 8
-// pieces) and 16 B loads, and the barrier that ends k-tile t waits for tile t + 1's A, issued three
-// k-tiles earlier (family 7: one).  Quarters run (0,0) (1,0) (1,1) (0,1) so each B half is dead for
-// half a k-tile before the next tile's copy of it is loaded into the same registers.  Every VMEM
-// op is issued whether or not its tile exists (kOOB offsets past the end: zeros, still counted), so
-// the counted vmcnt waits are exact.  Same products, per-accumulator MFMA order and epilogue as
-// families 6 / 7: bit-identical — and 1.5-1.7x slower (profiles/r6d_gemm_family10.txt): the four
-// waves of a column half each fetch the same W fragments, so a 64-k tile moves 160 KB through the
-// CU's vector-memory address path (family 7: 128 KB per two 32-k tiles, each byte once), which at
-// ~64 B/clk outlasts the tile's MFMA issue.  Development build only (tools/gemm_check, WSP_G7_XP).
-constexpr int kBStages = 4;
-template <int AM, bool CSK>
-__global__ __launch_bounds__(512, 1) void conv_gemm_gb(const ConvGemmArgs p, const __bf16* __restrict__ whi,
-                                                       const __bf16* __restrict__ wlo) {
-  constexpr bool DENSE = AM == 1;
-  static_assert(AM == 0 || AM == 1, "family 10: uniform k-tiles only");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int ntiles = p.N / 256;
-  const int mtiles = (p.M + 255) / 256;
-  const int wg = xcd_remap(blockIdx.x, ntiles * mtiles);
-  const int mt = wg / ntiles;
-  const int nt = wg - mt * ntiles;
-  const int m0 = mt * 256;
-  const int n0 = nt * 256;
-
-  // ---- A rows of this lane (family 7's mapping)
-  const int ac0 = 4 * ((lane & 7) ^ ((lane >> 4) & 1)), ac1 = ac0 ^ 16;
-  int a_r[4], a_t[DENSE ? 1 : 4], a_l[DENSE ? 1 : 4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + (4 * wave + i) * 8 + (lane >> 3);
-    if constexpr (DENSE) {
-      a_r[i] = m < p.M ? m : -1;
-    } else if (p.seg) {
-      const int mm = m < p.M ? m : p.M - 1;
-      const int b = seg_of(p.seg, p.nseg, mm);
-      const int t = (mm - p.seg[b]) * p.stride;
-      const int* is = p.iseg ? p.iseg : p.seg;
-      a_r[i] = is[b] + t;
-      a_t[i] = (m < p.M) ? t : -0x40000000;
-      a_l[i] = is[b + 1] - is[b];
-    } else {
-      const int b = m / p.T;
-      const int t = (m - b * p.T) * p.stride;
-      a_r[i] = b * p.Ti + t;
-      a_t[i] = (m < p.M) ? t : -0x40000000;
-      a_l[i] = p.Ti;
-    }
-  }
-  const int nk = p.Kp / BK;
-  int jt = 0, ct = 0;  // tap and channel of the next A k-tile to fetch (fetched in order)
-  auto dma_a = [&](int kt) {  // kt >= nk: the same pieces at kOOB (zeros into a stage nobody reads)
-    unsigned char* st = smem + (kt & (kBStages - 1)) * kGA;
-    const bool live = kt < nk;
-    const int off = jt * p.dil - p.pad;
-    const float* base = p.a[0];
-    int ld = p.lda[0], cl = ct;
-    if (ct >= p.cseg[2]) {
-      base = p.a[2];
-      ld = p.lda[2];
-      cl = ct - p.cseg[2];
-    } else if (ct >= p.cseg[1]) {
-      base = p.a[1];
-      ld = p.lda[1];
-      cl = ct - p.cseg[1];
-    }
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(base);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (DENSE) {
-        g_dma(ra, st + (4 * wave + i) * 1024,
-              live && a_r[i] >= 0 ? (a_r[i] * ld + cl + (i & 1 ? ac1 : ac0)) * 4 : kOOB);
-      } else {
-        const int tt = a_t[i] + off;
-        const bool ok = live && tt >= 0 && tt < a_l[i];
-        g_dma(ra, st + (4 * wave + i) * 1024, ok ? ((a_r[i] + off) * ld + cl + (i & 1 ? ac1 : ac0)) * 4 : kOOB);
-      }
-    }
-    ct += 32;
-    if (ct >= p.cin) {
-      ct -= p.cin;
-      ++jt;
-    }
-  };
-
-  const int wm = wave >> 1, wn = wave & 1;  // 4 x 2 waves of 64 x 128
-  const int r16 = lane & 15, qk = lane >> 4;
-  // B fragment (jh, j) of k-tile kt: column n0 + wn 128 + (4 jh + j) 16 + r16, k 32 kt + 8 qk .. + 7
-  const __amdgpu_buffer_rsrc_t rwh = make_rsrc(whi);
-  const __amdgpu_buffer_rsrc_t rwl = make_rsrc(wlo);
-  const int bcol0 = ((n0 + wn * 128 + r16) * p.Kp + 8 * qk) * 2;
-  const int bjstep = 16 * p.Kp * 2;
-  bf16x8 bh[2][4], bl[2][4];
-  auto load_b = [&](int kt, int jh) {
-    const bool live = kt < nk;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int o = live ? bcol0 + (4 * jh + j) * bjstep + kt * 64 : kOOB;
-      bh[jh][j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwh, o, 0, 0));
-      bl[jh][j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwl, o, 0, 0));
-    }
-  };
-
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 ah[2][2], al[2][2];
-  auto rdA = [&](const unsigned char* st, int ih) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = wm * 64 + (ih * 2 + i) * 16 + r16;
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk));
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(st + g_aslot(r, 2 * qk + 1));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 h0 = (__bf16)x0[e], h1 = (__bf16)x1[e];
-        ah[ih][i][e] = h0;
-        ah[ih][i][4 + e] = h1;
-        al[ih][i][e] = (__bf16)(x0[e] - (float)h0);
-        al[ih][i][4 + e] = (__bf16)(x1[e] - (float)h1);
-      }
-    }
-  };
-  auto mm = [&](int ih, int jh) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4& c = acc[ih * 2 + i][jh * 4 + j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[ih][i], bh[jh][j], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ih][i], bl[jh][j], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ih][i], bh[jh][j], c, 0, 0, 0);
-      }
-  };
-
-  // prologue: A tiles 0..3 and both B halves of tile 0, all waited for
-  dma_a(0);
-  dma_a(1);
-  dma_a(2);
-  dma_a(3);
-  load_b(0, 0);
-  load_b(0, 1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  // Per k-tile t, VMEM issue order: B half 0 of t + 1 (8), B half 1 of t + 1 (8), and after the
-  // barrier A of t + 4 (4).  Waits: B half 0 of t has B half 1 of t and A of t + 3 behind it (12);
-  // B half 1 of t has A of t + 3 and B half 0 of t + 1 behind it (12); A of t + 1 (issued after
-  // the barrier of t - 3) has 3 x 16 B loads and 2 x 4 A pieces behind it at the barrier of t (56).
-  for (int kt = 0; kt < nk; ++kt) {
-    const unsigned char* st = smem + (kt & (kBStages - 1)) * kGA;
-    // (the B registers' loads are register dependencies: hipcc places their vmcnt waits itself;
-    // only the LDS-DMA data below needs a counted wait)
-    rdA(st, 0);
-    mm(0, 0);
-    rdA(st, 1);  // its reads and split interleave with quarter (0,0)'s MFMAs
-    mm(1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    load_b(kt + 1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    mm(1, 1);
-    mm(0, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    load_b(kt + 1, 1);
-    // A of kt + 1 has landed and every wave is done reading this stage
-    asm volatile("s_waitcnt vmcnt(56) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    dma_a(kt + 4);
-  }
-  // every DMA (including the zero pieces past the end) has landed and every wave is past its
-  // last LDS read before the epilogue reuses LDS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-#define WSP_GBEPI(RB, RES)                                                                                  \
-  switch (p.act) {                                                                                         \
-    case kActRelu: g_epilogue_rows<kActRelu, RB, RES>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;    \
-    case kActTanh: g_epilogue_rows<kActTanh, RB, RES>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;    \
-    case kActGelu: g_epilogue_rows<kActGelu, RB, RES>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;    \
-    default: g_epilogue_rows<kActNone, RB, RES>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;          \
-  }
-  if constexpr (CSK) {
-    switch (p.act) {
-      case kActRelu: g_epilogue_cs<kActRelu>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;
-      case kActTanh: g_epilogue_cs<kActTanh>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;
-      case kActGelu: g_epilogue_cs<kActGelu>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;
-      default: g_epilogue_cs<kActNone>(p, acc, m0, n0, wm, wn, wave, lane, smem); break;
-    }
-  } else if (p.res) {
-    WSP_GBEPI(false, true)
-  } else if (p.row_bias) {
-    WSP_GBEPI(true, false)
-  } else {
-    WSP_GBEPI(false, false)
-  }
-#undef WSP_GBEPI
-}
-#endif  // WSP_G7_XP
 
 }  // namespace
 
@@ -889,56 +638,6 @@ void t_g256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t
     hipLaunchKernelGGL((conv_gemm_g<2, false>), dim3(nwg), dim3(512), lds, s, p, h, l);
   WSP_HIP(hipGetLastError());
 }
-
-#ifdef WSP_G7_XP
-// family 10 (development build): the operands family 7 takes on uniform k-tiles (no LayerNorm fold)
-bool gb256_supported(const ConvGemmArgs& p) {
-  return g256_supported(p) && uniform_ktiles(p) && !p.lnmode && p.Kp % BK == 0;
-}
-
-void t_gb256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t s) {
-  WSP_CHECK(gb256_supported(p), "conv_gemm_x3 family 10: unsupported operands");
-  const int nwg = ((p.M + 255) / 256) * (p.N / 256);
-  constexpr int lds0 = kBStages * kGA > kGEpiBytes ? kBStages * kGA : kGEpiBytes;
-  constexpr int lds = lds0 > kGCsBytes ? lds0 : kGCsBytes;
-  const bool dense = p.taps == 1 && p.pad == 0 && p.stride == 1 && !p.iseg && (p.seg || p.Ti == p.T);
-  if (p.colsum && dense)
-    hipLaunchKernelGGL((conv_gemm_gb<1, true>), dim3(nwg), dim3(512), lds, s, p, h, l);
-  else if (p.colsum)
-    hipLaunchKernelGGL((conv_gemm_gb<0, true>), dim3(nwg), dim3(512), lds, s, p, h, l);
-  else if (dense)
-    hipLaunchKernelGGL((conv_gemm_gb<1, false>), dim3(nwg), dim3(512), lds, s, p, h, l);
-  else
-    hipLaunchKernelGGL((conv_gemm_gb<0, false>), dim3(nwg), dim3(512), lds, s, p, h, l);
-  WSP_HIP(hipGetLastError());
-}
-
-// development entry (tools/gemm_check): plain family 7 operand forms (no LayerNorm fold)
-void t_g256_xp(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t s, int xp) {
-  const int nwg = ((p.M + 255) / 256) * (p.N / 256);
-  constexpr int lds0 = 2 * kGStage > kGEpiBytes ? 2 * kGStage : kGEpiBytes;
-  constexpr int lds = lds0 > kGCsBytes ? lds0 : kGCsBytes;
-  const bool dense = p.taps == 1 && p.pad == 0 && p.stride == 1 && !p.iseg && (p.seg || p.Ti == p.T);
-  const int am = !uniform_ktiles(p) ? 2 : dense ? 1 : 0;
-  WSP_CHECK(am != 2 && !p.lnmode, "t_g256_xp: AM 0 / 1 only");
-#define WSP_XPL(AMv, CS, XPv) hipLaunchKernelGGL((conv_gemm_g<AMv, CS, 0, XPv>), dim3(nwg), dim3(512), lds, s, p, h, l)
-  if (xp == 1) {
-    if (p.colsum) { if (am == 1) WSP_XPL(1, true, 1); else WSP_XPL(0, true, 1); }
-    else { if (am == 1) WSP_XPL(1, false, 1); else WSP_XPL(0, false, 1); }
-  } else if (xp == 3) {
-    WSP_CHECK(am == 1 && !p.colsum, "t_g256_xp 3: dense, no column sums");
-    WSP_XPL(1, false, 3);
-  } else if (xp == 4) {
-    WSP_CHECK(am == 1 && !p.colsum, "t_g256_xp 4: dense, no column sums");
-    WSP_XPL(1, false, 4);
-  } else {
-    if (p.colsum) { if (am == 1) WSP_XPL(1, true, 2); else WSP_XPL(0, true, 2); }
-    else { if (am == 1) WSP_XPL(1, false, 2); else WSP_XPL(0, false, 2); }
-  }
-#undef WSP_XPL
-  WSP_HIP(hipGetLastError());
-}
-#endif
 
 }  // namespace x3
 }  // namespace wsp

@@ -21,13 +21,12 @@
 //     the loop.
 // Blocks are ordered group-major behind the XCD remap, so the blocks resident on one XCD share
 // one or two groups' 1.2 MB weight slices in its L2.
+#include "bf16x3.h"
 #include "gemm_common.h"
 
 namespace wsp {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kCin = 48, kTaps = 128, kPad = 64, kK = kCin * kTaps;  // 6144
@@ -113,11 +112,7 @@ __global__ __launch_bounds__(512, 1) void pos_conv_kernel(const PosConvArgs p) {
       const bool ok = t >= 0 && t < T;
       const f32x4 v = bload4(rx, ok ? ((r0 + t) * p.ldx + g * kCin + 4 * c4) * 4 : kOOB);
       bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h[e] = (__bf16)v[e];
-        l[e] = (__bf16)(v[e] - (float)h[e]);
-      }
+      split(v, h, l);
       *reinterpret_cast<bf16x4*>(phi + row * 96 + 8 * c4) = h;
       *reinterpret_cast<bf16x4*>(plo + row * 96 + 8 * c4) = l;
     }
@@ -169,12 +164,7 @@ __global__ __launch_bounds__(512, 1) void pos_conv_kernel(const PosConvArgs p) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          f32x4& c = acc[i][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], c, 0, 0, 0);
-        }
+        for (int j = 0; j < 3; ++j) mma3(ah[i], al[i], bh[j], bl[j], acc[i][j]);
     }
   }
 

@@ -37,16 +37,13 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "bf16x3.h"
 #include "gemm_common.h"
 #include "res2_chain.h"
 
 namespace wsp {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPad = 4;  // image rows beyond each window edge (max dilation)
 
@@ -107,12 +104,7 @@ __global__ __launch_bounds__(NWv * 64, R == 128 ? NWv / 2 : 1) void res2_chain_k
     const int m = wr0 + ir - kPad;
     const f32x4 v = bload4(rx, (m >= 0 && m < p.M) ? (m * p.ldx + c) * 4 : kOOB);
     bf16x4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const __bf16 hh = (__bf16)v[e];
-      hi[e] = hh;
-      lo[e] = (__bf16)(v[e] - (float)hh);
-    }
+    split(v, hi, lo);
     const int a = G::addr(ir, c);
     *reinterpret_cast<bf16x4*>(xhi + a) = hi;
     *reinterpret_cast<bf16x4*>(xlo + a) = lo;
@@ -187,11 +179,7 @@ __global__ __launch_bounds__(NWv * 64, R == 128 ? NWv / 2 : 1) void res2_chain_k
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < TN; ++j) mma3(ah[i], al[i], bh[j], bl[j], acc[i][j]);
     wload(g + PD, bh, bl);
   };
   bf16x8 ah2[2][TM], al2[2][TM];
@@ -289,7 +277,6 @@ __global__ __launch_bounds__(NWv * 64, R == 128 ? NWv / 2 : 1) void res2_chain_k
   }
 }
 
-
 // ---- variant 4: halo-free strips (skewed chunk pipeline), W = 128 ----------
 // A block owns a strip of `rout` consecutive frame rows (about M / (2 x CUs):
 // one round of two blocks per CU) and walks it in chunks of kSR = 96 rows.  In
@@ -347,12 +334,7 @@ __global__ __launch_bounds__(256, 2) void res2_strip_kernel(const Res2Args p) {
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x);
   auto put4 = [&](int ir, int c, const f32x4& v) {
     bf16x4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const __bf16 hh = (__bf16)v[e];
-      hi[e] = hh;
-      lo[e] = (__bf16)(v[e] - (float)hh);
-    }
+    split(v, hi, lo);
     const int a = ir * kSRB + s_off(ir, c);
     *reinterpret_cast<bf16x4*>(xhi + a) = hi;
     *reinterpret_cast<bf16x4*>(xlo + a) = lo;
@@ -406,11 +388,7 @@ __global__ __launch_bounds__(256, 2) void res2_strip_kernel(const Res2Args p) {
   auto mma = [&](auto na, int g, const bf16x8 (&ah)[TM], const bf16x8 (&al)[TM], bf16x8& bh, bf16x8& bl) {
     constexpr int NA = decltype(na)::value;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh, acc[i], 0, 0, 0);
-    }
+    for (int i = 0; i < NA; ++i) mma3(ah[i], al[i], bh, bl, acc[i]);
     const int gn = g + PD;
     wload(gn >= kTotal ? gn - kTotal : gn, bh, bl);
     // keep the slot's reload right behind its MFMAs (hipcc otherwise sinks the whole

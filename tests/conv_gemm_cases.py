@@ -193,7 +193,7 @@ def ln_partials(x):
 
 def ln_images_colsum(w):
     """ln_cs[n] = sum_c of the bf16 hi + lo images of W'[n][c], an f64 sum rounded once
-    (model_impl.h: HLayer::fc1_cs)."""
+    (hubert_model.cpp: HLayer::fc1_cs)."""
     hi = to_bf16(w)
     lo = to_bf16(w - hi)
     return (hi.astype(np.float64) + lo.astype(np.float64)).sum(axis=1).astype(np.float32)

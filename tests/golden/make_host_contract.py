@@ -29,13 +29,14 @@ HANDLES = {
     "SimAM_ResNet100_ASP+feat64": ("SimAM_ResNet100_ASP", 64, 256, 0, 0),
     "HuBERT_base": ("HuBERT_base", 1, 768, 0, 0),
     "WavLM_base": ("WavLM_base", 1, 768, 0, 0),
+    "CAMPPlus": ("CAMPPlus", 80, 192, 0, 0),
 }
 # key: (a valid non-default-ish value, one value outside the accepted range)
 OPTIONS = {
     "precision": (0, 2), "streams": (5, 0), "layer": (6, 13), "in_planes": (32, 48), "res2_fused": (0, 2),
     "cat_gate": (0, 2), "res_prefetch": (0, 2), "res_tail": (2, 3), "sc_fuse": (1, 4), "c1_stage_fuse": (0, 2),
     "astp_fused": (0, 4), "attn_pipe": (0, 2), "pos_conv": (0, 2), "ln_fold": (1, 2), "tail_batch": (0, 2),
-    "res2_variant": (2, 1), "x3_variant": (3, 10), "conv3x3_img": (3, 4),
+    "res2_variant": (2, 1), "x3_variant": (3, 10), "conv3x3_img": (3, 4), "gate_fold": (0, 2), "cam_fused": (0, 2),
 }
 EXTRA_REFUSED = (("res2_variant", 5), ("x3_variant", -1), ("streams", 9), ("layer", -2), ("in_planes", 33))
 X3_ALIASES = (0, 1, 2, 6, 8, 9)

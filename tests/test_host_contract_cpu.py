@@ -32,7 +32,7 @@ def recorded():
 
 def test_every_handle_is_recorded(recorded):
     want, got = recorded
-    assert sorted(want) == sorted(got) == sorted(_generator().HANDLES) and len(want) == 10
+    assert sorted(want) == sorted(got) == sorted(_generator().HANDLES) and len(want) == 11
 
 
 @pytest.mark.parametrize("name", sorted(_generator().HANDLES))
@@ -78,3 +78,10 @@ def test_resnet_parameter_table(arch, two_emb):
 def test_simam_parameter_table(arch, in_planes):
     spec = A.make_spec(arch, acoustic_dim=80, embed_dim=256, in_planes=in_planes)
     assert _library_params(arch, 80, 256, in_planes=in_planes) == [(n, tuple(s)) for n, s in A.param_list(spec)]
+
+
+@pytest.mark.parametrize("arch", sorted(A.CAMPP_ARCHS))
+@pytest.mark.parametrize("feat_dim,embed_dim", ((80, 192), (64, 512)))
+def test_campplus_parameter_table(arch, feat_dim, embed_dim):
+    spec = A.make_spec(arch, feat_dim=feat_dim, embed_dim=embed_dim)
+    assert _library_params(arch, feat_dim, embed_dim) == [(n, tuple(s)) for n, s in A.param_list(spec)]

@@ -4,6 +4,7 @@
 // strided TDNN on the implicit GEMM, the three dense blocks on cam_dense.hip — each block one
 // buffer [B T'][Cmax] that its layers append 32 columns to in place — TSTP and the embedding.
 #include "cam_dense.h"
+#include "conv3x3_img.h"
 #include "fcm_conv.h"
 #include "model_impl.h"
 
@@ -17,10 +18,64 @@ const char* const kFcmBlocks[4] = {"head.layer1.0", "head.layer1.1", "head.layer
 std::string cam_layer_name(int bi, int li) {
   return "xvector.block" + std::to_string(bi + 1) + ".tdnnd" + std::to_string(li + 1);
 }
+
+// FCM head NHWC [B][F][T][32], then frame rows [B][T'][C]
+struct Campplus final : Model::Impl {
+  using Impl::Impl;
+  float *stem_w = nullptr, *stem_b = nullptr;  // head.conv1 + bn1
+  struct FcmBlock {
+    bool strided = false;  // first block of a stage: conv1 and the projection shortcut stride (2, 1)
+    // BN-folded weights and biases: conv1 as fcm_conv.hip fragments when strided, else as
+    // conv3x3_img.hip fragments like conv2; the shortcut as fcm_conv.hip fragments
+    void *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;
+    float *b1 = nullptr, *b2 = nullptr, *bsc = nullptr;
+  } fcm_blk[4];
+  void* fcm_out_w = nullptr;  // head.conv2 + bn2
+  float* fcm_out_b = nullptr;
+  ConvW cam_tdnn;
+  struct CamLayer {
+    int cin = 0;
+    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;  // nonlinear1 / nonlinear2 as affines
+    void *w1 = nullptr, *wl = nullptr;  // linear1 / linear_local as cam_pack_b fragments
+    LinW l1, l2;                        // the context mask's two linears
+  };
+  struct CamBlock {
+    std::vector<CamLayer> layers;
+    float *ts = nullptr, *tt = nullptr;  // transit BatchNorm
+    void* tw = nullptr;
+  } cam_blk[3];
+  float *cam_out_s = nullptr, *cam_out_t = nullptr;  // out_nonlinear
+  LinW cam_head;  // dense with its affine-free BatchNorm folded in
+  struct Ws {
+    float *X, *O, *Y1, *SC;         // FCM: [F][T][32] and [F/2][T][32] per utterance
+    float *D[3], *H, *Z, *S;        // dense buffers [M'][Cmax], h [M'][128], transit 3 [M'][512], unfused scratch
+    float *segsum, *mask, *pooled;  // [B][nseg][128], [B][nseg][32], [B][1024]
+    size_t floats;
+    int bc;  // utterances per forward chunk: the widest operand is the stem's output or a 1024-wide dense buffer
+  };
+
+  void build_params() override;
+  void finalize() override;
+  void check_forward(int B, int T) const override;
+  Ws ws_layout(int B, int T, float* base) const;
+  size_t ws_floats(int B, int T) const override { return ws_layout(B, T, nullptr).floats; }
+  void forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) override;
+};
 }  // namespace
 
+Model::Impl* make_campplus(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
+  // campplus.py:333-413: FCM head + dense TDNN, TSTP, embedding without an affine BatchNorm tail
+  if (arch != "CAMPPlus") return nullptr;
+  WSP_CHECK(!two_emb && !emb_bn, "CAMPPlus has no emb_bn / two_emb_layer");
+  WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "CAMPPlus feat_dim must be a positive multiple of 8");
+  WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
+  Campplus* m = new Campplus(arch, feat_dim, embed_dim, emb_bn, two_emb);
+  m->opt.x3_variant = 4;  // xvector.tdnn is the one implicit GEMM (N = 128)
+  return m;
+}
+
 // state_dict order of CAMPPlus(feat_dim, embed_dim) (937 entries)
-void Model::Impl::build_campp_params() {
+void Campplus::build_params() {
   add("head.conv1.weight", {32, 1, 3, 3});
   add_bn("head.bn1", 32);
   for (int i = 0; i < 4; ++i) {
@@ -62,7 +117,7 @@ void Model::Impl::build_campp_params() {
   add("xvector.dense.nonlinear.batchnorm.num_batches_tracked", {});
 }
 
-void Model::Impl::finalize_campp() {
+void Campplus::finalize() {
   auto up_affine = [&](const std::string& bn, float*& sc, float*& sh) {
     std::vector<double> a, b;
     bn_affine(bn, a, b);
@@ -75,28 +130,15 @@ void Model::Impl::finalize_campp() {
   WSP_CHECK(conv3x3_img_supported(32), "CAMPPlus: the 32-channel 3x3 image kernel is missing");
   auto fold_frag = [&](const std::string& wname, const std::string& bn, int taps, bool img, void*& frag,
                        float*& bias) {
-    std::vector<double> sc, sh;
-    bn_affine(bn, sc, sh);
-    std::vector<float> w = P(wname);
+    const Folded f = fold_bn(wname, bn);
     const int K = 32 * taps;
-    for (int n = 0; n < 32; ++n)
-      for (int k = 0; k < K; ++k) w[(size_t)n * K + k] = (float)(w[(size_t)n * K + k] * sc[n]);
-    const std::vector<float> wk = pack::conv_kmajor(w, 32, 32, taps, K);
+    const std::vector<float> wk = pack::conv_kmajor(f.w, 32, 32, taps, K);
     frag = img ? pack_frag(wk, 32, K) : up_frag(wk, 32, K);
-    bias = dev.upload(std::vector<float>(sh.begin(), sh.end()));
+    bias = dev.upload(f.b);
   };
-  {  // stem, as the ResNets'
-    std::vector<double> sc, sh;
-    bn_affine("head.bn1", sc, sh);
-    const auto& w = P("head.conv1.weight");
-    std::vector<float> wf(32 * 9), bf(32);
-    for (int c = 0; c < 32; ++c) {
-      for (int q = 0; q < 9; ++q) wf[c * 9 + q] = (float)(w[c * 9 + q] * sc[c]);
-      bf[c] = (float)sh[c];
-    }
-    stem_w = dev.upload(wf);
-    stem_b = dev.upload(bf);
-  }
+  const Folded stem = fold_bn("head.conv1.weight", "head.bn1");  // as the ResNets'
+  stem_w = dev.upload(stem.w);
+  stem_b = dev.upload(stem.b);
   for (int i = 0; i < 4; ++i) {
     const std::string p = kFcmBlocks[i];
     FcmBlock& fb = fcm_blk[i];
@@ -110,18 +152,14 @@ void Model::Impl::finalize_campp() {
     // xvector.tdnn: the reference's input channel c * F8 + f (FCM.forward's reshape) is our
     // frame-row column f * 32 + c
     const int F8 = feat_dim / 8, CF = 32 * F8;
-    std::vector<double> sc, sh;
-    bn_affine("xvector.tdnn.nonlinear.batchnorm", sc, sh);
-    const auto& W = P("xvector.tdnn.linear.weight");
-    std::vector<float> wp((size_t)128 * CF * 5), bf(128);
-    for (int n = 0; n < 128; ++n) {
+    const Folded t = fold_bn("xvector.tdnn.linear.weight", "xvector.tdnn.nonlinear.batchnorm");
+    std::vector<float> wp(t.w.size());
+    for (int n = 0; n < 128; ++n)
       for (int f = 0; f < F8; ++f)
         for (int c = 0; c < 32; ++c)
           for (int j = 0; j < 5; ++j)
-            wp[((size_t)n * CF + f * 32 + c) * 5 + j] = (float)(W[((size_t)n * CF + c * F8 + f) * 5 + j] * sc[n]);
-      bf[n] = (float)sh[n];
-    }
-    cam_tdnn = pack_conv(wp, 128, CF, 5, bf.data(), "");
+            wp[((size_t)n * CF + f * 32 + c) * 5 + j] = t.w[((size_t)n * CF + c * F8 + f) * 5 + j];
+    cam_tdnn = pack_conv(wp, 128, CF, 5, t.b.data(), "");
   }
   for (int bi = 0; bi < 3; ++bi) {
     CamBlock& cb = cam_blk[bi];
@@ -157,25 +195,18 @@ void Model::Impl::finalize_campp() {
   }
 }
 
-// utterances per forward chunk: the widest operand is the stem's output or a 1024-wide dense buffer
-int Model::Impl::campp_chunk(int B, int T) const {
-  const size_t Tp = (size_t)(T - 1) / 2 + 1;
-  return chunk_for(B, std::max((size_t)feat_dim * T * 32, Tp * 1024) * sizeof(float));
+void Campplus::check_forward(int, int T) const {
+  // as every family off the f32 GEMM path: the message names the first of them
+  WSP_CHECK(opt.precision == 1, "ResNet runs on the bf16x3 kernels only (precision=1)");
+  WSP_CHECK(T >= 3, "CAMPPlus needs >= 3 frames (2 after the stride-2 TDNN)");
 }
 
-namespace {
-struct CamWs {
-  float *X, *O, *Y1, *SC;         // FCM: [F][T][32] and [F/2][T][32] per utterance
-  float *D[3], *H, *Z, *S;        // dense buffers [M'][Cmax], h [M'][128], transit 3 [M'][512], unfused scratch
-  float *segsum, *mask, *pooled;  // [B][nseg][128], [B][nseg][32], [B][1024]
-  size_t floats;
-};
-CamWs cam_ws(const Model::Impl& m, int B, int T, float* base) {
-  const size_t bc = m.campp_chunk(B, T);
-  const size_t Tp = (size_t)(T - 1) / 2 + 1, Mp = bc * Tp, nseg = (Tp + kCamSeg - 1) / kCamSeg;
-  const size_t F = m.feat_dim;
+Campplus::Ws Campplus::ws_layout(int B, int T, float* base) const {
+  const size_t Tp = (size_t)(T - 1) / 2 + 1, nseg = (Tp + kCamSeg - 1) / kCamSeg, F = feat_dim;
   WsCursor c{base};
-  CamWs w;
+  Ws w;
+  w.bc = chunk_for(B, std::max(F * T * 32, Tp * 1024) * sizeof(float));
+  const size_t bc = w.bc, Mp = bc * Tp;
   w.X = c.take(bc * F * T * 32);
   w.O = c.take(bc * F * T * 32);
   w.Y1 = c.take(bc * (F / 2) * T * 32);
@@ -190,13 +221,10 @@ CamWs cam_ws(const Model::Impl& m, int B, int T, float* base) {
   w.floats = c.off;
   return w;
 }
-}  // namespace
 
-size_t Model::Impl::campp_ws_floats(int B, int T) const { return cam_ws(*this, B, T, nullptr).floats; }
-
-void Model::Impl::forward_campp(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
-  const int bc = campp_chunk(B, T);
-  const CamWs W = cam_ws(*this, B, T, ws);
+void Campplus::forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
+  const Ws W = ws_layout(B, T, ws);
+  const int bc = W.bc;
   const int Tp = (T - 1) / 2 + 1;
   static const char* kGemm[3] = {"cam_gemm.b1", "cam_gemm.b2", "cam_gemm.b3"};
   static const char* kLocal[3] = {"cam_local.b1", "cam_local.b2", "cam_local.b3"};
@@ -252,7 +280,7 @@ void Model::Impl::forward_campp(const float* feats, int B, int T, float* embed, 
       auto gemm_pro = [&](const char* tag, int K, int N, const float* s1, const float* t1, const void* w,
                           const float* s2, const float* t2, float* out, int ldo, float* segsum) {
         CamGemmArgs a{D, ld, M, Tp, K, N, s1, t1, w, s2, t2, out, ldo, segsum};
-        if (!cam_fused) {  // A/B option: the BN-ReLU as an elementwise pass of its own
+        if (!opt.cam_fused) {  // A/B option: the BN-ReLU as an elementwise pass of its own
           run("cam_bnrelu", 0, s, [&] { launch_cam_bnrelu(D, ld, M, K, s1, t1, W.S, 1024, s); });
           a.a = W.S;
           a.lda = 1024;

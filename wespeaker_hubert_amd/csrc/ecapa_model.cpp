@@ -11,11 +11,58 @@
 //   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
 //           -> online-softmax attentive mean/std          -> [B][3072]
 //   head    BN(3072) + Linear (+ bn2) folded into one GEMV -> embed [B][D]
+#include "astp_fused.h"
 #include "model_impl.h"
+#include "res2_chain.h"
 
 namespace wsp {
 
-void Model::Impl::build_ecapa_params() {
+namespace {
+struct Ecapa final : Model::Impl {
+  using Impl::Impl;
+  int C = 512;
+  bool glob = false;
+  ConvW layer1;
+  struct Block {
+    ConvW c1, c3, res2[7];
+    LinW se1, se2;
+    // the 7 Res2Net convs packed for res2_chain.hip (one launch per block)
+    void* r2w = nullptr;
+    float *r2b = nullptr, *r2s = nullptr, *r2t = nullptr;
+  } blk[3];
+  ConvW conv, pool1, pool2;
+  ConvW conv_g;                // conv with W_b + W_c in its middle third (option "cat_gate")
+  void* pool2_frag = nullptr;  // pool.linear2 in MFMA B-fragment order for astp_fused.hip
+  LinW pool1_ctx;
+  LinW head;
+
+  void build_params() override;
+  void pack_res2(Block& b, const std::string& p, int w);
+  void finalize() override;
+  int chunk(int B, int T) const;
+  size_t ws_floats(int B, int T) const override;
+  void forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) override;
+  // seg (device [B+1] row offsets) non-null: ragged batch of M rows; T unused by the
+  // kernels then (per-utterance lengths come from seg).
+  void forward_chunk(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
+                     const int* seg = nullptr, int M_seg = 0);
+};
+}  // namespace
+
+Model::Impl* make_ecapa(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
+  if (arch != "ECAPA_TDNN_c512" && arch != "ECAPA_TDNN_GLOB_c512" && arch != "ECAPA_TDNN_c1024" &&
+      arch != "ECAPA_TDNN_GLOB_c1024")
+    return nullptr;
+  WSP_CHECK(feat_dim > 0 && feat_dim % 4 == 0, "ECAPA feat_dim must be a positive multiple of 4");
+  WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
+  Ecapa* m = new Ecapa(arch, feat_dim, embed_dim, emb_bn, two_emb);
+  m->opt.x3_variant = 7;  // 6 (the 256 x 256 tile on 16x16x32 MFMAs, r3) with LDS-DMA staging (r4)
+  m->C = (arch.find("c1024") != std::string::npos) ? 1024 : 512;
+  m->glob = arch.find("GLOB") != std::string::npos;
+  return m;
+}
+
+void Ecapa::build_params() {
   const int64_t C = this->C, w = C / 8;
   add("layer1.conv.weight", {C, feat_dim, 5});
   add("layer1.conv.bias", {C});
@@ -52,7 +99,7 @@ void Model::Impl::build_ecapa_params() {
 
 // Res2Net chain weights for res2_chain.hip (pack::frag_res2); conv bias and eval-BN affine per
 // step [7][w].
-void Model::Impl::pack_res2(Block& b, const std::string& p, int w) {
+void Ecapa::pack_res2(Block& b, const std::string& p, int w) {
   const std::vector<float>* W[7];
   std::vector<float> bias((size_t)7 * w), sc((size_t)7 * w), sh((size_t)7 * w);
   for (int i = 0; i < 7; ++i) {
@@ -73,7 +120,7 @@ void Model::Impl::pack_res2(Block& b, const std::string& p, int w) {
   b.r2t = dev.upload(sh);
 }
 
-void Model::Impl::finalize_ecapa() {
+void Ecapa::finalize() {
   const int w = C / 8;
   layer1 = pack_conv(P("layer1.conv.weight"), C, feat_dim, 5, P("layer1.conv.bias").data(), "layer1.bn");
   for (int li = 0; li < 3; ++li) {
@@ -139,8 +186,8 @@ void Model::Impl::finalize_ecapa() {
 
 // utterances per ECAPA forward chunk (uniform batches): the widest activation operand is the
 // [M][1536] ASTP input / logits; larger batches run as consecutive chunks over one chunk-sized
-// workspace (as resnet_chunk)
-int Model::Impl::ecapa_chunk(int B, int T) const {
+// workspace, as the other families
+int Ecapa::chunk(int B, int T) const {
   return chunk_for(B, (size_t)T * std::max(C, 1536) * sizeof(float));
 }
 
@@ -174,18 +221,27 @@ EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base) {
 }
 }  // namespace
 
-size_t Model::Impl::ecapa_ws_floats(int B, size_t M) const { return ecapa_ws(C, B, M, nullptr).floats; }
+size_t Ecapa::ws_floats(int B, int T) const {
+  const size_t bc = chunk(B, T);
+  return ecapa_ws(C, bc, bc * T, nullptr).floats;
+}
 
-void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
-                                const int* seg, int M_seg) {
+void Ecapa::forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
+  const int bc = chunk(B, T);
+  for (int c0 = 0; c0 < B; c0 += bc)
+    forward_chunk(feats + (size_t)c0 * T * feat_dim, std::min(bc, B - c0), T, embed + (size_t)c0 * embed_dim, ws, s);
+}
+
+void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
+                          const int* seg, int M_seg) {
   const int M = seg ? M_seg : B * T, w = C / 8;
   const EcapaWs W = ecapa_ws(C, B, M, ws);
   float* const* x = W.x;
   float *h1 = W.h1, *h2 = W.h2, *h3 = W.h3, *xp = W.xp;
   // SE squeeze fused into conv3's epilogue (per-utterance f64 column sums) on the
   // bf16x3 path for uniform batches whose utterances span >= one block of rows
-  const int se_bm = precision == 1 ? conv_gemm_x3_block_rows(ConvGemmArgs{.N = C}, x3_variant) : 0;
-  const bool se_fused = precision == 1 && !seg && T >= se_bm;
+  const int se_bm = opt.precision == 1 ? conv_gemm_x3_block_rows(ConvGemmArgs{.N = C}, opt.x3_variant) : 0;
+  const bool se_fused = opt.precision == 1 && !seg && T >= se_bm;
   // a GEMM whose three A slots (set by the caller) cat / add different [M][C] tensors
   auto gemm3 = [&](const char* tag, ConvGemmArgs& g, const ConvW& cw, int dil, int pad, float* out, int ldo) {
     g.lda[0] = g.lda[1] = g.lda[2] = C;
@@ -204,16 +260,16 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
   gcat.cseg[2] = 2 * C;
   gcat.cseg[3] = 3 * C;
   gcat.lda[0] = gcat.lda[1] = gcat.lda[2] = C;
-  const ConvW& wcat = cat_gate ? conv_g : conv;
+  const ConvW& wcat = opt.cat_gate ? conv_g : conv;
   bool fold = false;
-  if (cat_gate && gate_fold && precision == 1) {
+  if (opt.cat_gate && opt.gate_fold && opt.precision == 1) {
     ConvGemmArgs g = gcat;
     g.a[2] = h3;
     g.gate = W.gate;
     g.ldg = C;
     g.gate_k0 = 2 * C;
     fill(g, wcat, M, T, 1, 0, xp, 1536, kActRelu, nullptr, true, seg, B);
-    fold = conv_gemm_x3_gate_ok(g, x3_variant);
+    fold = conv_gemm_x3_gate_ok(g, opt.x3_variant);
     if (fold) gcat = g;
   }
 
@@ -223,7 +279,7 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
     const int dil = li + 2;
     const float* xin = x[li + 1];
     gemm("conv1x1_CxC", b.c1, xin, C, h1, C, M, T, 1, 0, kActRelu, s, seg, B, nullptr, true, 1);
-    if (precision == 1 && res2_fused && b.r2w) {
+    if (opt.precision == 1 && opt.res2_fused && b.r2w) {
       // the whole chain in one launch (res2_chain.hip)
       Res2Args r{};
       r.x = h1;
@@ -232,7 +288,7 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
       r.M = M;
       r.T = T;
       r.dil = dil;
-      r.variant = w == 128 ? res2_variant : std::min(res2_variant, 3);
+      r.variant = w == 128 ? opt.res2_variant : std::min(opt.res2_variant, 3);
       r.rout = res2_chain_rout(dil, r.variant, M);
       r.seg = seg;
       r.nseg = B;
@@ -277,7 +333,7 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
     // gate_fold: not even that — conv_cat reads h3 and the gate (x[4] stays unwritten)
     if (li == 2 && fold) continue;
     run("se.scale", 0, s, [&] {
-      launch_residual_scale(cat_gate && li == 2 ? nullptr : xin, h3, W.gate, x[li + 2], B, T, C, s, seg, M);
+      launch_residual_scale(opt.cat_gate && li == 2 ? nullptr : xin, h3, W.gate, x[li + 2], B, T, C, s, seg, M);
     });
   }
   gemm3("conv_cat", gcat, wcat, 1, 0, xp, 1536);
@@ -289,7 +345,7 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
   }
   // GLOB: the context's per-utterance row bias carries pool.linear1's bias
   gemm("pool_linear1", pool1, xp, 1536, W.att, 128, M, T, 1, 0, kActTanh, s, seg, B, glob ? W.rowb : nullptr, !glob);
-  if (precision == 1 && astp_fused_on) {
+  if (opt.precision == 1 && opt.astp_fused) {
     // linear2 + softmax over frames + attentive mean / std in one pass (astp_fused.hip)
     AstpArgs a{W.att, xp, 1536, B, T, 1536, seg, pool2_frag, pool2.bias, 1e-7f, W.pooled};
     run("astp", 2.0 * M * 1536 * 128, s, [&] { launch_astp_fused(a, s); });
@@ -300,6 +356,30 @@ void Model::Impl::forward_ecapa(const float* feats, int B, int T, float* embed, 
   run("head", 0, s, [&] {
     launch_small_linear({W.pooled, 3072, head.wt, head.bias, embed, embed_dim, B, 3072, embed_dim, 0}, s);
   });
+}
+
+// ------------------------------------------------------------ Model API ---
+static Ecapa& as_ecapa(Model::Impl* m) {
+  Ecapa* e = dynamic_cast<Ecapa*>(m);
+  WSP_CHECK(e, "segmented batches are implemented for ECAPA-TDNN handles");
+  return *e;
+}
+
+size_t Model::workspace_bytes_segments(int B, int M) const {
+  const Ecapa& m = as_ecapa(impl);
+  WSP_CHECK(B > 0 && M >= B, "segmented batch needs B >= 1 and M >= B rows");
+  return ecapa_ws(m.C, B, M, nullptr).floats * sizeof(float) + 256;
+}
+
+void Model::forward_segments(const float* feats, int B, const int* seg, int M, float* embed, void* ws,
+                             size_t ws_bytes, hipStream_t s) {
+  Ecapa& m = as_ecapa(impl);
+  WSP_CHECK(m.finalized, "forward before finalize");
+  WSP_CHECK(seg != nullptr && B > 0 && M >= B, "segmented batch needs offsets, B >= 1 and M >= B rows");
+  WSP_CHECK((size_t)M * 1536 < (1u << 31) / 4, "segmented batch too large");
+  WSP_CHECK(ws_bytes >= workspace_bytes_segments(B, M), "workspace too small");
+  float* wsf = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+  m.forward_chunk(feats, B, 1, embed, wsf, s, seg, M);  // T unused when segmented
 }
 
 }  // namespace wsp

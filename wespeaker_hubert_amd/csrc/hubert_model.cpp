@@ -33,9 +33,88 @@ const char* const kPre = "frontend.upstream.upstream.model.";
 
 std::string hp(const std::string& n) { return std::string(kPre) + n; }
 
+// Batch plan: utterance ranges of the feature extractor, their row counts per conv level, and the
+// int32 offset tables.
+struct HubertChunk {
+  int b0 = 0, b1 = 0;
+  size_t off = 0;       // index of this chunk's tables in HubertPlan::offs
+  size_t rows[7] = {};  // conv-level frame rows of the chunk
+  size_t samples = 0, sample0 = 0, row6 = 0;
+  size_t row3 = 0;  // the chunk's first row in the batch-wide level-3 rows (cnn_tail_batch)
+  int maxT0 = 0;
+};
+struct HubertPlan {
+  int B = 0;
+  size_t M = 0, Mout = 0, maxA = 0, maxB = 0;
+  // batch-wide rows of conv levels 3..5 and whether CNN layers 4..6 run once over the batch
+  // (their global offsets follow seg6 | fseg in offs as seg3 | seg4 | seg5)
+  size_t M3 = 0, M4 = 0, M5 = 0;
+  bool tail_batch = false;
+  int maxChunk = 0, maxT6 = 0;
+  size_t maxStats = 0;  // doubles of conv0 partial moments (hubert_conv0_stats_doubles) of the largest chunk
+  std::vector<HubertChunk> chunks;
+  std::vector<int> offs;
+};
+
+// channels-last [B][T][C]
+struct Hubert final : Model::Impl {
+  using Impl::Impl;
+  // WavLM Base / Base+ (arch "WavLM_base"): HuBERT-base plus the gated relative-position bias
+  bool wavlm = false;
+  float* h_conv0_w = nullptr;  // [512][10]
+  float *h_gn_g = nullptr, *h_gn_b = nullptr;
+  ConvW h_conv[7];  // 1..6: strided feature-extractor convs (GELU epilogue)
+  float *h_ln0_g = nullptr, *h_ln0_b = nullptr;
+  ConvW h_proj, h_pos;
+  float *h_enc_g = nullptr, *h_enc_b = nullptr;
+  struct HLayer {
+    ConvW qkv, out, fc1, fc2;
+    float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
+    // LayerNorm fold (option ln_fold): fc1 on the un-normalised rows with gamma1 folded into W
+    // and W beta1 into the bias; fc1_cs[n] = sum_c W'[n][c] (of the bf16 hi + lo images)
+    ConvW fc1f;
+    float* fc1_cs = nullptr;
+    float* gate_w = nullptr;  // WavLM: [wa (64) | wb (64) | ba | bb | grep_a (12)] (attn.h launch_attn_gate)
+  };
+  float* h_rel_tab = nullptr;  // WavLM: [12][kAttnRelStride] bias per head over d = key - query in [-778, 778]
+  std::vector<HLayer> h_layers;
+  std::vector<float> h_fw;  // featurizer weight per hidden state
+
+  void build_params() override;
+  void finalize() override;
+  bool owns_option(const std::string& key) const override { return key == "layer"; }
+  bool is_frontend() const override { return true; }
+  // wav -> frames only: Model refuses its feats -> embedding calls on a front-end handle before these
+  size_t ws_floats(int, int) const override { throw InvalidArg{"front-end handle: no embedding forward"}; }
+  void forward(const float*, int, int, float*, float*, hipStream_t) override { ws_floats(0, 0); }
+  HubertPlan plan(int B, const int* lens) const;
+  size_t ws_bytes(const HubertPlan& pl) const;  // one range's workspace slice, 256-byte granules
+  void forward(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws, hipStream_t s);
+};
+
+// the front-end entry points' way to their handle; `what`: the refusal of any other handle
+Hubert& as_hubert(Model::Impl* m, const char* what) {
+  Hubert* h = dynamic_cast<Hubert*>(m);
+  WSP_CHECK(h, what);
+  return *h;
+}
+
 }  // namespace
 
-void Model::Impl::build_hubert_params() {
+Model::Impl* make_hubert(const std::string& arch, int, int embed_dim, bool emb_bn, bool two_emb) {
+  // s3prl HuBERT-base / WavLM Base(+) upstream + Featurizer (frontend/s3prl.py); input is
+  // the waveform, output 768-dim frames (S3prlFrontend.output_size()).  WavLM_base is the
+  // HuBERT-base network with a gated relative-position bias in every attention.
+  if (arch != "HuBERT_base" && arch != "WavLM_base") return nullptr;
+  WSP_CHECK(embed_dim == 768, arch + " output size is 768");
+  Hubert* m = new Hubert(arch, 1, embed_dim, emb_bn, two_emb);
+  m->wavlm = arch == "WavLM_base";
+  m->opt.x3_variant = 7;  // every GEMM whose operands family 7 takes (r4), the rest on 6
+  m->opt.streams = 2;     // HuBERT + ECAPA C4 chain +2.6 %
+  return m;
+}
+
+void Hubert::build_params() {
   for (int i = 0; i < 7; ++i) {
     add(hp("feature_extractor.conv_layers." + std::to_string(i) + ".0.weight"),
         {kConvDim, i == 0 ? 1 : kConvDim, kConvK[i]});
@@ -89,7 +168,7 @@ static int wavlm_rel_bucket(int d) {
   return b + std::min(big, n - 1);
 }
 
-void Model::Impl::finalize_hubert() {
+void Hubert::finalize() {
   h_conv0_w = dev.upload(P(hp("feature_extractor.conv_layers.0.0.weight")));
   h_gn_g = dev.upload(P(hp("feature_extractor.conv_layers.0.2.weight")));
   h_gn_b = dev.upload(P(hp("feature_extractor.conv_layers.0.2.bias")));
@@ -210,8 +289,8 @@ void Model::Impl::finalize_hubert() {
   // normalize=False), or a one-hot pick for `layer != -1` (s3prl.py:84-87).
   const auto& fw = P("frontend.featurizer.weights");
   h_fw.assign(kLayers + 1, 0.f);
-  if (h_layer_sel >= 0) {
-    h_fw[h_layer_sel] = 1.f;
+  if (opt.layer >= 0) {
+    h_fw[opt.layer] = 1.f;
   } else {
     double mx = fw[0], sum = 0.0;
     for (float x : fw) mx = std::max(mx, (double)x);
@@ -220,17 +299,11 @@ void Model::Impl::finalize_hubert() {
   }
 }
 
-int Model::Impl::hubert_cnn_frames(int N, int upto) const {
-  int t = N;
-  for (int i = 0; i <= upto; ++i) t = (t - kConvK[i]) / kConvS[i] + 1;
-  return t;
-}
-
 // Host-side plan of one (uniform or ragged) batch: frames per conv level,
 // feature-extractor chunks whose conv0 output stays below 2 GiB (32-bit buffer
 // offsets; 33 MB per 5 s utterance), and the int32 offset tables the kernels
 // read (uploaded into the workspace).
-HubertPlan Model::Impl::hubert_plan(int B, const int* lens) const {
+HubertPlan Hubert::plan(int B, const int* lens) const {
   HubertPlan pl;
   pl.B = B;
   std::vector<int> T[7], Tout(B);
@@ -292,7 +365,7 @@ HubertPlan Model::Impl::hubert_plan(int B, const int* lens) const {
   pl.maxT6 = *std::max_element(T[6].begin(), T[6].end());
   // layers 4..6 batch-wide: more than one chunk, level-3 rows within a 2 GiB operand, and the
   // chunk buffers (free after the chunk loop) large enough for the level-4 / level-5 rows
-  pl.tail_batch = tail_batch && pl.chunks.size() > 1 && pl.M3 * kConvDim * sizeof(float) < kOperandCap &&
+  pl.tail_batch = opt.tail_batch && pl.chunks.size() > 1 && pl.M3 * kConvDim * sizeof(float) < kOperandCap &&
                   pl.M4 <= pl.maxA && pl.M5 <= pl.maxB;
   WSP_CHECK(pl.M * kFfn * sizeof(float) < ((size_t)1 << 31) - 64,
             "HuBERT batch too large for one call (frames * 3072 floats must stay below 2 GiB)");
@@ -331,10 +404,11 @@ HubertWs hubert_ws(const HubertPlan& pl, bool wavlm, float* base) {
 }
 }  // namespace
 
-size_t Model::Impl::hubert_ws_floats(const HubertPlan& pl) const { return hubert_ws(pl, wavlm, nullptr).floats; }
+size_t Hubert::ws_bytes(const HubertPlan& pl) const {
+  return (hubert_ws(pl, wavlm, nullptr).floats * sizeof(float) + 255) & ~size_t(255);
+}
 
-void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws,
-                                 hipStream_t s) {
+void Hubert::forward(const float* wav, const HubertPlan& pl, float* feats, int cmn, float* ws, hipStream_t s) {
   const HubertWs W = hubert_ws(pl, wavlm, ws);
   float *cnnA = W.cnnA, *cnnB = W.cnnB, *x = W.x, *x1 = W.x1, *qkv = W.qkv, *ao = W.ao, *ffn = W.ffn;
   double* stats = W.stats;
@@ -371,11 +445,11 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
     // default 7 (and 8) every one of these GEMMs (N % 256 == 0) takes the LDS-DMA 16x16x32 tile, which
     // is faster than the register-staged 16x16x32 tile for QKV and out_proj too (tools/gemm_check,
     // profiles/r5a_gemm_check.txt: qkv / out_proj / fc1 / fc2 / cnn.c1 per launch, families 6 vs 7)
-    const bool mf16 = x3_variant == 5 && (std::strncmp(tag, "h_cnn", 5) == 0 || std::strcmp(tag, "h_fc1") == 0 ||
+    const bool mf16 = opt.x3_variant == 5 && (std::strncmp(tag, "h_cnn", 5) == 0 || std::strcmp(tag, "h_fc1") == 0 ||
                                           std::strcmp(tag, "h_fc2") == 0);
     run(tag, 2.0 * rows * (gcols ? (double)cw.N * kPosGin / kPosGout : cw.N) * cw.K, s, [&] {
-      if (precision == 1)
-        launch_conv_gemm_x3(g, cw.whi, cw.wlo, mf16 ? 6 : x3_variant, s);
+      if (opt.precision == 1)
+        launch_conv_gemm_x3(g, cw.whi, cw.wlo, mf16 ? 6 : opt.x3_variant, s);
       else
         launch(g, cw, s);
     });
@@ -396,11 +470,11 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
     a.ldo = D;
     a.M = rows;
     a.D = D;
-    if (layer >= 0 && (h_fw[layer] != 0.f || (h_layer_sel < 0 && layer == 0))) {
+    if (layer >= 0 && (h_fw[layer] != 0.f || (opt.layer < 0 && layer == 0))) {
       // weighted mode initialises at hidden state 0; one-hot mode at the chosen one
       a.feat = feats;
       a.feat_w = h_fw[layer];
-      a.feat_init = (h_layer_sel >= 0 || layer == 0) ? 1 : 0;
+      a.feat_init = (opt.layer >= 0 || layer == 0) ? 1 : 0;
       a.seg = seg6;
       a.fseg = fseg;
       a.nseg = B;
@@ -447,7 +521,7 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
   ln("h_ln", cnn6, nullptr, cnn6, M, kConvDim, h_ln0_g, h_ln0_b, -1);
   conv("h_proj", h_proj, cnn6, kConvDim, x, kHidden, M, M, 1, 0, kActNone, nullptr, true, nullptr, nullptr, 0);
   // ---- encoder: x + GELU(pos_conv(x)) -> LN  (SamePad: pad 64, last output dropped)
-  if (precision == 1 && pos_conv) {
+  if (opt.precision == 1 && opt.pos_conv) {
     // direct grouped conv over the same packed weights (pos_conv.hip): 48 of 64 columns per group
     // computed, input patch split once per block
     run("h_pos_conv", 2.0 * M * kHidden * (double)h_pos.K, s, [&] {
@@ -460,7 +534,7 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
   }
   ln("h_ln", x, pc, x, M, kHidden, h_enc_g, h_enc_b, 0);
   // LayerNorm fold: the GEMMs it touches run on tile family 7 (x3_variant 7, bf16x3)
-  const bool fold = ln_fold && precision == 1 && x3_variant == 7;
+  const bool fold = opt.ln_fold && opt.precision == 1 && opt.x3_variant == 7;
   for (int l = 0; l < kLayers; ++l) {
     const HLayer& L = h_layers[l];
     conv("h_qkv", L.qkv, x, kHidden, qkv, 3 * kHidden, M, M, 1, 0, kActNone, nullptr, true, nullptr, nullptr, 0);
@@ -468,7 +542,7 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
     if (wavlm)  // the gate comes from the layer input x, not from q
       run("h_gate", 4.0 * M * kHidden, s, [&] { launch_attn_gate(x, kHidden, M, kHeads, L.gate_w, gate, s); });
     run("h_attn", 4.0 * B * kHeads * (double)pl.maxT6 * pl.maxT6 * (kHidden / kHeads), s, [&] {
-      launch_attn(qkv, 3 * kHidden, ao, kHidden, B, pl.maxT6, kHeads, kHidden / kHeads, s, seg6, attn_pipe,
+      launch_attn(qkv, 3 * kHidden, ao, kHidden, B, pl.maxT6, kHeads, kHidden / kHeads, s, seg6, opt.attn_pipe,
                   wavlm ? &ab : nullptr);
     });
     if (fold) {
@@ -503,31 +577,27 @@ void Model::Impl::forward_hubert(const float* wav, const HubertPlan& pl, float* 
 }
 
 // ------------------------------------------------------------ Model API ---
-bool Model::is_frontend() const { return impl->hubert; }
+bool Model::is_frontend() const { return impl->is_frontend(); }
 
 int Model::out_frames(int N) const {
-  WSP_CHECK(impl->hubert, "out_frames: not a front-end handle");
+  as_hubert(impl, "out_frames: not a front-end handle");
   WSP_CHECK(N >= 1, "HuBERT needs at least 1 sample");
   return (N + kDownsample - 1) / kDownsample;
 }
 
 size_t Model::frontend_workspace_bytes(int B, int N) const {
-  WSP_CHECK(impl->hubert, "frontend_workspace_bytes: not a front-end handle");
+  as_hubert(impl, "frontend_workspace_bytes: not a front-end handle");
   WSP_CHECK(B > 0 && N >= 1, "HuBERT needs B >= 1 and N >= 1 samples");
   const std::vector<int> lens(B, N);
   return frontend_workspace_bytes_segments(B, lens.data());
 }
 
 size_t Model::frontend_workspace_bytes_segments(int B, const int* lens) const {
-  WSP_CHECK(impl->hubert, "frontend_workspace_bytes: not a front-end handle");
+  const Hubert& m = as_hubert(impl, "frontend_workspace_bytes: not a front-end handle");
   WSP_CHECK(B > 0 && lens, "HuBERT needs B >= 1 utterances");
-  const int ns = impl->nsub(B);
+  const int ns = m.nsub(B);
   size_t bytes = 256;
-  for (int i = 0; i < ns; ++i) {
-    const int b0 = B * i / ns, b1 = B * (i + 1) / ns;
-    bytes += (impl->hubert_ws_floats(impl->hubert_plan(b1 - b0, lens + b0)) * sizeof(float) + 255) &
-             ~size_t(255);
-  }
+  for (int i = 0; i < ns; ++i) bytes += m.ws_bytes(m.plan(B * (i + 1) / ns - B * i / ns, lens + B * i / ns));
   return bytes;
 }
 
@@ -540,8 +610,7 @@ void Model::forward_frontend(const float* wav, int B, int N, float* feats, int c
 
 void Model::forward_frontend_segments(const float* wav, int B, const int* lens, float* feats, int* frame_offsets,
                                       int cmn, void* ws, size_t ws_bytes, hipStream_t s) {
-  Impl& m = *impl;
-  WSP_CHECK(m.hubert, "forward_frontend: not a front-end handle");
+  Hubert& m = as_hubert(impl, "forward_frontend: not a front-end handle");
   WSP_CHECK(m.finalized, "forward before finalize");
   WSP_CHECK(B > 0 && lens, "HuBERT needs B >= 1 utterances");
   WSP_CHECK(ws_bytes >= frontend_workspace_bytes_segments(B, lens), "workspace too small");
@@ -551,7 +620,7 @@ void Model::forward_frontend_segments(const float* wav, int B, const int* lens, 
   std::vector<HubertPlan> pls(ns);
   for (int i = 0; i < ns; ++i) {
     const int b0 = B * i / ns, b1 = B * (i + 1) / ns;
-    pls[i] = m.hubert_plan(b1 - b0, lens + b0);
+    pls[i] = m.plan(b1 - b0, lens + b0);
   }
   if (frame_offsets) {
     frame_offsets[0] = 0;
@@ -568,8 +637,8 @@ void Model::forward_frontend_segments(const float* wav, int B, const int* lens, 
   size_t sample0 = 0, frame0 = 0;
   for (int i = 0; i < ns; ++i) {
     const HubertPlan& pl = pls[i];
-    m.forward_hubert(wav + sample0, pl, feats + frame0 * kHidden, cmn, reinterpret_cast<float*>(wsb), m.sub(s, i));
-    wsb += (m.hubert_ws_floats(pl) * sizeof(float) + 255) & ~size_t(255);
+    m.forward(wav + sample0, pl, feats + frame0 * kHidden, cmn, reinterpret_cast<float*>(wsb), m.sub(s, i));
+    wsb += m.ws_bytes(pl);
     for (int b = B * i / ns; b < B * (i + 1) / ns; ++b) sample0 += lens[b];
     frame0 += pl.Mout;
   }

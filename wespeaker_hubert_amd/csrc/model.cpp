@@ -1,8 +1,9 @@
 // Speaker-model runtime, the part every family shares: the Model API, parameter intake
 // (reference state_dict order), pack-and-upload helpers (BatchNorm folding and packing run on
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
-// The families' tables, folds, workspace layouts and forward schedules are in ecapa_model.cpp,
-// resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp and campplus_model.cpp.
+// The families derive from Model::Impl: their tables, folds, workspace layouts and forward
+// schedules are in ecapa_model.cpp, resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp
+// and campplus_model.cpp; Model::create below is the one place here that names them.
 #include "model_impl.h"
 
 namespace wsp {
@@ -44,6 +45,15 @@ void Model::Impl::bn_affine(const std::string& p, std::vector<double>& sc, std::
     sc[i] = (double)w[i] / std::sqrt((double)rv[i] + kBnEps);
     sh[i] = (double)b[i] - (double)rm[i] * sc[i];
   }
+}
+
+Model::Impl::Folded Model::Impl::fold_bn(const std::string& wname, const std::string& bn) const {
+  std::vector<double> sc, sh;
+  bn_affine(bn, sc, sh);
+  Folded f{P(wname), std::vector<float>(sh.begin(), sh.end())};
+  const size_t K = f.w.size() / sc.size();
+  for (size_t i = 0; i < f.w.size(); ++i) f.w[i] = (float)(f.w[i] * sc[i / K]);
+  return f;
 }
 
 // ------------------------------------------------------ pack and upload ---
@@ -112,8 +122,8 @@ void Model::Impl::fill(ConvGemmArgs& g, const ConvW& cw, int M, int T, int dil, 
 }
 
 void Model::Impl::launch(const ConvGemmArgs& g, const ConvW& cw, hipStream_t s) {
-  if (precision == 1)
-    launch_conv_gemm_x3(g, cw.whi, cw.wlo, x3_variant, s);
+  if (opt.precision == 1)
+    launch_conv_gemm_x3(g, cw.whi, cw.wlo, opt.x3_variant, s);
   else
     launch_conv_gemm(g, s);
 }
@@ -151,99 +161,30 @@ void Model::Impl::join(hipStream_t s, int ns) {
 }
 
 // ------------------------------------------------------------ Model API ---
-Model::Model() : impl(new Impl) {}
-Model::~Model() {
-  for (auto& kv : impl->prof_map)
+Model::Impl::~Impl() {
+  for (auto& kv : prof_map)
     for (auto& e : kv.second.ev) {
       (void)hipEventDestroy(e.first);
       (void)hipEventDestroy(e.second);
     }
-  for (auto t : impl->sub_st) (void)hipStreamDestroy(t);
-  for (auto e : impl->sub_ev) (void)hipEventDestroy(e);
-  delete impl;
+  for (auto t : sub_st) (void)hipStreamDestroy(t);
+  for (auto e : sub_ev) (void)hipEventDestroy(e);
 }
 
+Model::~Model() { delete impl; }
+
 void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
-  Impl& m = *impl;
-  m.arch = arch;
-  m.feat_dim = feat_dim;
-  m.embed_dim = embed_dim;
-  m.emb_bn = emb_bn;
-  m.two_emb = two_emb;
+  WSP_CHECK(!impl, "model already created");
+  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus})
+    if ((impl = make(arch, feat_dim, embed_dim, emb_bn, two_emb))) break;
+  WSP_CHECK(impl, "unsupported arch " + arch);
   // Creation and parameter intake are host-only; the device is bound at
   // finalize (create's device when one was current).
-  if (hipGetDevice(&m.device) != hipSuccess) {
+  if (hipGetDevice(&impl->device) != hipSuccess) {
     (void)hipGetLastError();
-    m.device = -1;
+    impl->device = -1;
   }
-  if (arch == "ECAPA_TDNN_c512" || arch == "ECAPA_TDNN_GLOB_c512" || arch == "ECAPA_TDNN_c1024" ||
-      arch == "ECAPA_TDNN_GLOB_c1024") {
-    m.ecapa = true;
-    m.x3_variant = 7;  // 6 (the 256 x 256 tile on 16x16x32 MFMAs, r3) with LDS-DMA staging (r4)
-    m.C = (arch.find("c1024") != std::string::npos) ? 1024 : 512;
-    m.glob = arch.find("GLOB") != std::string::npos;
-    WSP_CHECK(feat_dim > 0 && feat_dim % 4 == 0, "ECAPA feat_dim must be a positive multiple of 4");
-    WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
-    m.build_ecapa_params();
-  } else if (arch.rfind("ResNet", 0) == 0) {
-    static const std::map<std::string, std::pair<bool, std::vector<int>>> kRes = {
-        {"ResNet18", {false, {2, 2, 2, 2}}},     {"ResNet34", {false, {3, 4, 6, 3}}},
-        {"ResNet50", {true, {3, 4, 6, 3}}},      {"ResNet101", {true, {3, 4, 23, 3}}},
-        {"ResNet152", {true, {3, 8, 36, 3}}},    {"ResNet221", {true, {6, 16, 48, 3}}},
-        {"ResNet293", {true, {10, 20, 64, 3}}}};
-    auto it = kRes.find(arch);
-    WSP_CHECK(it != kRes.end(), "unsupported arch " + arch);
-    // resnet.py:124 sizes the pooling for int(feat_dim / 8) frequency rows while stage 4 keeps
-    // ceil(feat_dim / 8): the reference model only runs for multiples of 8
-    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "ResNet feat_dim must be a positive multiple of 8");
-    m.ecapa = false;
-    // basic blocks: 256 x 128 swizzled (with the residual prefetch, ROLE 2: +1.3 % C3 over variant 3,
-    // r2c); bottleneck ResNets: family 7 wherever it takes the operands (1x1 convs with N % 256 == 0),
-    // family 6 elsewhere — ResNet293 C3 +0.2-0.4 % over 4 in three interleaved pairs (r6u)
-    m.x3_variant = it->second.first ? 7 : 4;
-    m.streams = 2;     // two utterance ranges in flight: ResNet293 C3 +8.6 %
-    m.bottleneck = it->second.first;
-    for (int i = 0; i < 4; ++i) m.nblocks[i] = it->second.second[i];
-    m.build_resnet_params();
-  } else if (arch == "SimAM_ResNet34_ASP" || arch == "SimAM_ResNet100_ASP") {
-    // samresnet.py:124-166: in_planes 64 (option "in_planes" before the weights),
-    // acoustic_dim = feat_dim, basic SimAM blocks [3,4,6,3] / [6,16,24,3]
-    WSP_CHECK(!two_emb && !emb_bn, "SimAM-ResNet has no emb_bn / two_emb_layer");
-    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "SimAM-ResNet acoustic_dim must be a multiple of 8");
-    WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
-    m.ecapa = false;
-    m.simam = true;
-    m.bottleneck = false;
-    m.x3_variant = 5;  // MFMA-bound 3x3 convs (K = 9C): wide tiles where N % 256 == 0 (+6 % over variant 3)
-    m.streams = 2;     // SimAM-ResNet100 +3.8 %
-    m.m_ch = 64;
-    const int nb34[4] = {3, 4, 6, 3}, nb100[4] = {6, 16, 24, 3};
-    for (int i = 0; i < 4; ++i) m.nblocks[i] = arch == "SimAM_ResNet34_ASP" ? nb34[i] : nb100[i];
-    m.build_simam_params();
-  } else if (arch == "HuBERT_base" || arch == "WavLM_base") {
-    // s3prl HuBERT-base / WavLM Base(+) upstream + Featurizer (frontend/s3prl.py); input is
-    // the waveform, output 768-dim frames (S3prlFrontend.output_size()).  WavLM_base is the
-    // HuBERT-base network with a gated relative-position bias in every attention.
-    WSP_CHECK(embed_dim == 768, arch + " output size is 768");
-    m.ecapa = false;
-    m.hubert = true;
-    m.wavlm = arch == "WavLM_base";
-    m.feat_dim = 1;
-    m.x3_variant = 7;  // every GEMM whose operands family 7 takes (r4), the rest on 6
-    m.streams = 2;  // HuBERT + ECAPA C4 chain +2.6 %
-    m.build_hubert_params();
-  } else if (arch == "CAMPPlus") {
-    // campplus.py:333-413: FCM head + dense TDNN, TSTP, embedding without an affine BatchNorm tail
-    WSP_CHECK(!two_emb && !emb_bn, "CAMPPlus has no emb_bn / two_emb_layer");
-    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "CAMPPlus feat_dim must be a positive multiple of 8");
-    WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
-    m.ecapa = false;
-    m.campp = true;
-    m.x3_variant = 4;  // xvector.tdnn is the one implicit GEMM (N = 128)
-    m.build_campp_params();
-  } else {
-    throw InvalidArg{"unsupported arch " + arch};
-  }
+  impl->build_params();
 }
 
 int Model::num_params() const { return (int)impl->params.size(); }
@@ -274,16 +215,7 @@ void Model::finalize() {
   for (auto& p : m.params)
     WSP_CHECK(p.set || p.name.find("num_batches_tracked") != std::string::npos,
               "parameter not set: " + p.name);
-  if (m.ecapa)
-    m.finalize_ecapa();
-  else if (m.simam)
-    m.finalize_simam();
-  else if (m.hubert)
-    m.finalize_hubert();
-  else if (m.campp)
-    m.finalize_campp();
-  else
-    m.finalize_resnet();
+  m.finalize();
   for (auto& p : m.params) std::vector<float>().swap(p.host);
   m.finalized = true;
 }
@@ -291,17 +223,9 @@ void Model::finalize() {
 int Model::embed_dim() const { return impl->embed_dim; }
 int Model::feat_dim() const { return impl->feat_dim; }
 
-// workspace of one sub-batch of B utterances, 256-byte granules
-size_t Model::Impl::ws_bytes_one(int B, int T) const {
-  const int bc = ecapa ? ecapa_chunk(B, T) : B;
-  const size_t f = ecapa   ? ecapa_ws_floats(bc, (size_t)bc * T)
-                   : campp ? campp_ws_floats(B, T)
-                           : resnet_ws_floats(B, T);
-  return (f * sizeof(float) + 255) & ~size_t(255);
-}
-
+// one workspace slice per sub-batch, 256-byte granules
 size_t Model::workspace_bytes(int B, int T) const {
-  WSP_CHECK(!impl->hubert, "HuBERT handle: use the front-end workspace query");
+  WSP_CHECK(!impl->is_frontend(), "HuBERT handle: use the front-end workspace query");
   const int ns = impl->nsub(B);
   size_t bytes = 256;
   for (int i = 0; i < ns; ++i) bytes += impl->ws_bytes_one(B * (i + 1) / ns - B * i / ns, T);
@@ -311,14 +235,12 @@ size_t Model::workspace_bytes(int B, int T) const {
 void Model::forward(const float* feats, int B, int T, float* embed, void* ws, size_t ws_bytes,
                     hipStream_t s) {
   Impl& m = *impl;
-  WSP_CHECK(!m.hubert, "HuBERT handle: use the front-end forward");
+  WSP_CHECK(!m.is_frontend(), "HuBERT handle: use the front-end forward");
   WSP_CHECK(m.finalized, "forward before finalize");
   WSP_CHECK(B > 0 && T > 1, "forward needs B >= 1 and T >= 2 frames");
   WSP_CHECK((size_t)B * T < (1u << 31), "B*T too large");
   WSP_CHECK(ws_bytes >= workspace_bytes(B, T), "workspace too small");
-  WSP_CHECK(m.ecapa || m.precision == 1, "ResNet runs on the bf16x3 kernels only (precision=1)");
-  WSP_CHECK(!m.simam || (T + 7) / 8 >= 2, "SimAM-ResNet needs >= 2 frames after the three stride-2 stages");
-  WSP_CHECK(!m.campp || T >= 3, "CAMPPlus needs >= 3 frames (2 after the stride-2 TDNN)");
+  m.check_forward(B, T);
   char* wsb = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
   const int ns = m.nsub(B);
   if (ns > 1) m.fork(s, ns);
@@ -326,41 +248,10 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
     const int b0 = B * i / ns, nb = B * (i + 1) / ns - b0;
     const float* f = feats + (size_t)b0 * T * m.feat_dim;
     float* e = embed + (size_t)b0 * m.embed_dim;
-    float* wsf = reinterpret_cast<float*>(wsb);
-    const hipStream_t si = m.sub(s, i);
-    if (m.ecapa) {
-      // consecutive utterance chunks whose operands stay < 2 GiB, over one chunk-sized workspace
-      const int bc = m.ecapa_chunk(nb, T);
-      for (int c0 = 0; c0 < nb; c0 += bc)
-        m.forward_ecapa(f + (size_t)c0 * T * m.feat_dim, std::min(bc, nb - c0), T, e + (size_t)c0 * m.embed_dim, wsf,
-                        si);
-    } else if (m.simam)
-      m.forward_simam(f, nb, T, e, wsf, si);
-    else if (m.campp)
-      m.forward_campp(f, nb, T, e, wsf, si);
-    else
-      m.forward_resnet(f, nb, T, e, wsf, si);
+    m.forward(f, nb, T, e, reinterpret_cast<float*>(wsb), m.sub(s, i));
     wsb += m.ws_bytes_one(nb, T);
   }
   if (ns > 1) m.join(s, ns);
-}
-
-size_t Model::workspace_bytes_segments(int B, int M) const {
-  WSP_CHECK(impl->ecapa, "segmented batches are implemented for ECAPA-TDNN handles");
-  WSP_CHECK(B > 0 && M >= B, "segmented batch needs B >= 1 and M >= B rows");
-  return impl->ecapa_ws_floats(B, (size_t)M) * sizeof(float) + 256;
-}
-
-void Model::forward_segments(const float* feats, int B, const int* seg, int M, float* embed, void* ws,
-                             size_t ws_bytes, hipStream_t s) {
-  Impl& m = *impl;
-  WSP_CHECK(m.ecapa, "segmented batches are implemented for ECAPA-TDNN handles");
-  WSP_CHECK(m.finalized, "forward before finalize");
-  WSP_CHECK(seg != nullptr && B > 0 && M >= B, "segmented batch needs offsets, B >= 1 and M >= B rows");
-  WSP_CHECK((size_t)M * 1536 < (1u << 31) / 4, "segmented batch too large");
-  WSP_CHECK(ws_bytes >= workspace_bytes_segments(B, M), "workspace too small");
-  float* wsf = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
-  m.forward_ecapa(feats, B, 1, embed, wsf, s, seg, M);  // T unused when segmented
 }
 
 void Model::profile(bool on) {
@@ -372,22 +263,22 @@ void Model::profile(bool on) {
   impl->prof = on;
 }
 
-// One table behind set_option and get_option: key, Impl member, accepted range [lo, hi] without
+// One table behind set_option and get_option: key, Options member, accepted range [lo, hi] without
 // `hole`, and the refusal's message.
 namespace {
 struct Opt {
   const char* key;
-  int Model::Impl::*field;
+  int Options::*field;
   int lo, hi, hole;
   const char* err;
 };
-using I = Model::Impl;
+using I = Options;
 constexpr int kNoHole = -1000;
 const Opt kOpts[] = {
     {"precision", &I::precision, 0, 1, kNoHole, "precision must be 0 (f32) or 1 (bf16x3)"},
     {"streams", &I::streams, 1, 8, kNoHole, "streams must be 1..8"},
-    {"layer", &I::h_layer_sel, -1, 12, kNoHole, "layer must be -1 (weighted sum) or 0..12"},
-    {"in_planes", &I::m_ch, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
+    {"layer", &I::layer, -1, 12, kNoHole, "layer must be -1 (weighted sum) or 0..12"},
+    {"in_planes", &I::in_planes, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
     {"res2_fused", &I::res2_fused, 0, 1, kNoHole, "res2_fused must be 0 or 1"},
     {"cam_fused", &I::cam_fused, 0, 1, kNoHole, "cam_fused must be 0 (separate BN-ReLU pass) or 1 (GEMM prologue)"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
@@ -396,7 +287,7 @@ const Opt kOpts[] = {
     {"res_tail", &I::res_tail, 0, 2, kNoHole, "res_tail must be 0 (off), 1 (tail + next conv1) or 2 (tail alone)"},
     {"sc_fuse", &I::sc_fuse, 0, 3, kNoHole, "sc_fuse must be 0 .. 3 (bit 0: one GEMM, bit 1: in the tail)"},
     {"c1_stage_fuse", &I::c1_stage_fuse, 0, 1, kNoHole, "c1_stage_fuse must be 0 or 1"},
-    {"astp_fused", &I::astp_fused_on, 0, 3, kNoHole,
+    {"astp_fused", &I::astp_fused, 0, 3, kNoHole,
      "astp_fused must be 0 (linear2 GEMM + pooling kernel) or 1 (fused)"},
     {"attn_pipe", &I::attn_pipe, 0, 1, kNoHole, "attn_pipe must be 0 or 1"},
     {"pos_conv", &I::pos_conv, 0, 1, kNoHole,
@@ -409,7 +300,7 @@ const Opt kOpts[] = {
      "or 4 (halo-free strips, c1024 widths; else as 3)"},
     {"x3_variant", &I::x3_variant, 0, 9, kNoHole,
      "x3_variant must be 3, 4, 5, 6 (5 on 16x16x32 MFMAs) or 7 (6 staged by LDS-DMA)"},
-    {"conv3x3_img", &I::conv3x3_img_on, 0, 3, kNoHole,
+    {"conv3x3_img", &I::conv3x3_img, 0, 3, kNoHole,
      "conv3x3_img must be 0 (off), 1 (32 / 64 channels) or 2 / 3 (also 128)"},
 };
 const Opt& find_opt(const std::string& key) {
@@ -425,10 +316,10 @@ void Model::set_option(const std::string& key, int value) {
   if (key == "attn_lds" || key == "conv1x1_rows") return;
   const Opt& o = find_opt(key);
   if (key == "layer") {
-    WSP_CHECK(m.hubert, "option 'layer' applies to the HuBERT front end");
+    WSP_CHECK(m.owns_option(key), "option 'layer' applies to the HuBERT front end");
     WSP_CHECK(!m.finalized, "option 'layer' must be set before finalize");
   } else if (key == "in_planes") {
-    WSP_CHECK(m.simam, "option 'in_planes' applies to SimAM-ResNet handles");
+    WSP_CHECK(m.owns_option(key), "option 'in_planes' applies to SimAM-ResNet handles");
     WSP_CHECK(!m.finalized, "option 'in_planes' must be set before finalize");
     WSP_CHECK(value == 32 || value == 64, o.err);
     for (const auto& p : m.params) WSP_CHECK(!p.set, "option 'in_planes' must be set before the weights");
@@ -441,11 +332,11 @@ void Model::set_option(const std::string& key, int value) {
   } else if (key == "astp_fused") {
     value = value ? 1 : 0;  // 2 / 3: former fused variants (r3 pruned), deprecated aliases of 1
   }
-  m.*o.field = value;
-  if (key == "in_planes") m.build_simam_params();  // the parameter table follows the stem width
+  m.opt.*o.field = value;
+  if (key == "in_planes") m.build_params();  // the parameter table follows the stem width
 }
 
-int Model::get_option(const std::string& key) const { return impl->*find_opt(key).field; }
+int Model::get_option(const std::string& key) const { return impl->opt.*find_opt(key).field; }
 
 void Model::profile_query(const std::string& tag, int* launches, double* total_ms, double* flops) {
   // `tag` names one kernel class or, as a prefix "tag.", every sub-class under it

@@ -10,7 +10,7 @@ namespace wsp {
 
 class Model {
  public:
-  Model();
+  Model() = default;  // empty until create() builds the arch's family object
   ~Model();
   void create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
   int num_params() const;
@@ -46,7 +46,7 @@ class Model {
   struct Impl;
 
  private:
-  Impl* impl;
+  Impl* impl = nullptr;
 };
 
 }  // namespace wsp

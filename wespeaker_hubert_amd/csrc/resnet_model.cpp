@@ -2,19 +2,124 @@
 // folding / packing, workspace and the two forward schedules.  The two share the stem, the block
 // table (RBlock), the chunk rule, the 2-D implicit GEMM and the 3x3 dispatch; NHWC activations
 // [B][F][T][C].
+#include "conv3x3_img.h"
 #include "model_impl.h"
 
 namespace wsp {
 
+namespace {
+// ResNet (resnet.py:110-260), NHWC activations [B][F][T][C]; `simam`: SimAM-ResNet
+// (samresnet.py:20-166): basic blocks whose bn2 output passes SimAM before the shortcut add, ASP
+// pooling, `bottleneck` Linear.  The stem width is option "in_planes".
+struct ResNet final : Model::Impl {
+  using Impl::Impl;
+  bool simam = false;
+  bool bottleneck = true;
+  int nblocks[4] = {0, 0, 0, 0};
+  float *stem_w = nullptr, *stem_b = nullptr;  // <pre>conv1 + bn1
+  bool img_ok(const ConvW& cw, int C) const { return cw.frag && opt.conv3x3_img && (C <= 64 || opt.conv3x3_img >= 2); }
+  struct RBlock {
+    ConvW c1, c2, c3, sc;
+    // conv3 (bn3 folded) and the projection shortcut (its bn folded) as ONE 1x1 GEMM over
+    // [y2 | strided x] (K = planes + in_planes, bias b3 + b_sc): the shortcut's output never goes
+    // through HBM (option "sc_fuse"; bottleneck blocks off the fused-tail path, N % 256 == 0)
+    ConvW c3sc;
+    void* w3acc = nullptr;  // conv3 (bn3 folded) as pack_frag_acc B fragments for bottleneck_tail
+    // [conv3 | shortcut] (both BN-folded) for the in-tail shortcut (BottleneckTailArgs::xsc) and its
+    // summed bias: a stride-1 first block with in_planes == planes == 32
+    void* w3scx = nullptr;
+    float* b3scx = nullptr;
+    void* w1frag = nullptr;  // conv1 (bn1 folded) as pack_frag B fragments: run inside the previous block's tail
+    bool has_sc = false;
+    int stride = 1, in_planes = 0, planes = 0, out_planes = 0;
+    std::string name;    // state_dict prefix, "[front.]layer<li + 1>.<bi>"
+    int li = 0, bi = 0;  // stage, block within the stage
+  };
+  std::vector<RBlock> rblocks;
+  LinW seg1, seg2;  // seg2: two_emb_layer's seg_2 with the affine-free seg_bn_1 folded in
+  ConvW asp1, asp2;  // SimAM-ResNet: ASP attention, `bottleneck`
+  LinW simam_head;
+  // one chunk's regions; y1_floats / y2_floats: the (padded) sizes of Y1 / Y2, which the heads reuse
+  // as split-K scratch.  From `part` on: SimAM-ResNet only.
+  struct Ws {
+    float *X, *O, *Y1, *Y2, *SC, *pooled;
+    double* part = nullptr;  // f64 moment partials
+    float *coef = nullptr, *Xt = nullptr, *att = nullptr, *logit = nullptr;
+    size_t y1_floats, y2_floats, floats;
+    int bc;  // utterances per forward chunk, by the widest activation operand of any block
+  };
+
+  void build_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn);
+  void build_params() override;
+  bool owns_option(const std::string& key) const override { return simam && key == "in_planes"; }
+  ConvW pack_conv_bn(const std::string& wname, const std::string& bn, int N, int cin, int taps,
+                     void** acc_frag = nullptr, void** b_frag = nullptr);
+  void finalize_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn);
+  void finalize() override;
+  void finalize_simam();
+  void check_forward(int B, int T) const override;
+  Ws ws_layout(int B, int T, float* base) const;
+  size_t ws_floats(int B, int T) const override { return ws_layout(B, T, nullptr).floats; }
+  void gemm2d(const char* tag, const ConvW& cw, const float* a0, int lda, float* out, int ldo, int B, int Fi, int Ti,
+              int kw, int stride, int pad, int act, const float* res, int ldres, hipStream_t s);
+  void gemm1x1(const char* tag, const ConvW& cw, const float* a0, float* out, int M, int act, const float* res,
+               hipStream_t s);
+  void gemm_c3sc(const char* tag, const RBlock& rb, const float* y2, const float* x, int Ci, float* out, int B, int Fi,
+                 int Ti, int Fo, int To, hipStream_t s);
+  void conv3x3(const char* tag, const ConvW& cw, const float* in, int ldin, float* out, int B, int Fi, int Ti,
+               int stride, bool relu, const float* res, hipStream_t s);
+  void forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) override;
+  void forward_simam(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s);
+};
+}  // namespace
+
+Model::Impl* make_resnet(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
+  // bottleneck?, blocks per stage; SimAM (samresnet.py:124-166): basic SimAM blocks
+  struct Arch {
+    const char* name;
+    bool simam, bottleneck;
+    int nblocks[4];
+  };
+  static const Arch kArchs[] = {
+      {"ResNet18", false, false, {2, 2, 2, 2}},           {"ResNet34", false, false, {3, 4, 6, 3}},
+      {"ResNet50", false, true, {3, 4, 6, 3}},            {"ResNet101", false, true, {3, 4, 23, 3}},
+      {"ResNet152", false, true, {3, 8, 36, 3}},          {"ResNet221", false, true, {6, 16, 48, 3}},
+      {"ResNet293", false, true, {10, 20, 64, 3}},        {"SimAM_ResNet34_ASP", true, false, {3, 4, 6, 3}},
+      {"SimAM_ResNet100_ASP", true, false, {6, 16, 24, 3}}};
+  const Arch* a = std::find_if(std::begin(kArchs), std::end(kArchs), [&](const Arch& k) { return arch == k.name; });
+  if (a == std::end(kArchs)) return nullptr;
+  if (a->simam) {
+    WSP_CHECK(!two_emb && !emb_bn, "SimAM-ResNet has no emb_bn / two_emb_layer");
+    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "SimAM-ResNet acoustic_dim must be a multiple of 8");
+    WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
+  } else {
+    // resnet.py:124 sizes the pooling for int(feat_dim / 8) frequency rows while stage 4 keeps
+    // ceil(feat_dim / 8): the reference model only runs for multiples of 8
+    WSP_CHECK(feat_dim >= 8 && feat_dim % 8 == 0, "ResNet feat_dim must be a positive multiple of 8");
+  }
+  ResNet* m = new ResNet(arch, feat_dim, embed_dim, emb_bn, two_emb);
+  m->simam = a->simam;
+  m->bottleneck = a->bottleneck;
+  std::copy(a->nblocks, a->nblocks + 4, m->nblocks);
+  // SimAM: MFMA-bound 3x3 convs (K = 9C): wide tiles where N % 256 == 0 (+6 % over variant 3).
+  // Basic blocks: 256 x 128 swizzled (with the residual prefetch, ROLE 2: +1.3 % C3 over variant 3,
+  // r2c); bottleneck ResNets: family 7 wherever it takes the operands (1x1 convs with N % 256 == 0),
+  // family 6 elsewhere — ResNet293 C3 +0.2-0.4 % over 4 in three interleaved pairs (r6u)
+  m->opt.x3_variant = a->simam ? 5 : a->bottleneck ? 7 : 4;
+  m->opt.streams = 2;  // two utterance ranges in flight: ResNet293 C3 +8.6 %, SimAM-ResNet100 +3.8 %
+  if (a->simam) m->opt.in_planes = 64;  // samresnet.py:124 (option "in_planes" before the weights)
+  return m;
+}
+
 // Stem and block table under `pre`; a block's projection shortcut is <block>.<sc_conv> / .<sc_bn>.
 // Parameter order is the reference state_dict's.
-void Model::Impl::build_res_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn) {
+void ResNet::build_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn) {
   const int exp = bottleneck ? 4 : 1, k1 = bottleneck ? 1 : 3;
-  add(pre + "conv1.weight", {m_ch, 1, 3, 3});
-  add_bn(pre + "bn1", m_ch);
-  int in_planes = m_ch;
+  add(pre + "conv1.weight", {opt.in_planes, 1, 3, 3});
+  add_bn(pre + "bn1", opt.in_planes);
+  int in_planes = opt.in_planes;
   for (int li = 0; li < 4; ++li) {
-    const int planes = m_ch << li;
+    const int planes = opt.in_planes << li;
     for (int bi = 0; bi < nblocks[li]; ++bi) {
       RBlock rb;
       rb.name = pre + "layer" + std::to_string(li + 1) + "." + std::to_string(bi);
@@ -44,9 +149,27 @@ void Model::Impl::build_res_blocks(const std::string& pre, const char* sc_conv, 
   }
 }
 
-void Model::Impl::build_resnet_params() {
-  build_res_blocks("", "shortcut.0", "shortcut.1");
-  const int stats_dim = (feat_dim / 8) * m_ch * 8 * (bottleneck ? 4 : 1);
+// state_dict of SimAM_ResNet{34,100}_ASP (samresnet.py:72-166): front.* backbone,
+// pooling.attention.{0,2,3} (ASP, pooling_layers.py:151-173), bottleneck.  Rebuilt when option
+// "in_planes" changes the stem width.
+void ResNet::build_params() {
+  params.clear();
+  idx.clear();
+  rblocks.clear();
+  if (simam) {
+    build_blocks("front.", "downsample.0", "downsample.1");
+    const int CF = 8 * opt.in_planes * (feat_dim / 8);  // ASP: in_planes * 8 * int(acoustic_dim / 8)
+    add("pooling.attention.0.weight", {128, CF, 1});
+    add("pooling.attention.0.bias", {128});
+    add_bn("pooling.attention.2", 128);
+    add("pooling.attention.3.weight", {CF, 128, 1});
+    add("pooling.attention.3.bias", {CF});
+    add("bottleneck.weight", {embed_dim, 2 * CF});
+    add("bottleneck.bias", {embed_dim});
+    return;
+  }
+  build_blocks("", "shortcut.0", "shortcut.1");
+  const int stats_dim = (feat_dim / 8) * opt.in_planes * 8 * (bottleneck ? 4 : 1);
   add("seg_1.weight", {embed_dim, stats_dim * 2});
   add("seg_1.bias", {embed_dim});
   if (two_emb) {  // resnet.py:158-161: BatchNorm1d(affine=False) + seg_2
@@ -58,33 +181,10 @@ void Model::Impl::build_resnet_params() {
   }
 }
 
-// state_dict of SimAM_ResNet{34,100}_ASP (samresnet.py:72-166): front.* backbone,
-// pooling.attention.{0,2,3} (ASP, pooling_layers.py:151-173), bottleneck.  Rebuilt when option
-// "in_planes" changes the stem width.
-void Model::Impl::build_simam_params() {
-  params.clear();
-  idx.clear();
-  rblocks.clear();
-  build_res_blocks("front.", "downsample.0", "downsample.1");
-  const int CF = 8 * m_ch * (feat_dim / 8);  // ASP: in_planes * 8 * int(acoustic_dim / 8)
-  add("pooling.attention.0.weight", {128, CF, 1});
-  add("pooling.attention.0.bias", {128});
-  add_bn("pooling.attention.2", 128);
-  add("pooling.attention.3.weight", {CF, 128, 1});
-  add("pooling.attention.3.bias", {CF});
-  add("bottleneck.weight", {embed_dim, 2 * CF});
-  add("bottleneck.bias", {embed_dim});
-}
-
 // conv -> BN (eval) folded into the weights: W' = W * s[n], bias = shift.
-ConvW Model::Impl::pack_conv_bn(const std::string& wname, const std::string& bn, int N, int cin, int taps,
-                                void** acc_frag, void** b_frag) {
-  std::vector<double> sc, sh;
-  bn_affine(bn, sc, sh);
-  std::vector<float> w = P(wname);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < cin * taps; ++k) w[(size_t)n * cin * taps + k] = (float)(w[(size_t)n * cin * taps + k] * sc[n]);
-  const std::vector<float> b(sh.begin(), sh.begin() + N);
+ConvW ResNet::pack_conv_bn(const std::string& wname, const std::string& bn, int N, int cin, int taps,
+                            void** acc_frag, void** b_frag) {
+  const auto [w, b] = fold_bn(wname, bn);
   ConvW cw = pack_conv(w, N, cin, taps, b.data(), "");
   if (acc_frag) *acc_frag = pack_frag_acc(w, N, cin * taps);
   if (b_frag) *b_frag = pack_frag(w, N, cin * taps);
@@ -95,19 +195,10 @@ ConvW Model::Impl::pack_conv_bn(const std::string& wname, const std::string& bn,
 }
 
 // The stem and every block's convs with their BatchNorms folded in, for both families.
-void Model::Impl::finalize_res_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn) {
-  {
-    std::vector<double> sc, sh;
-    bn_affine(pre + "bn1", sc, sh);
-    const auto& w = P(pre + "conv1.weight");
-    std::vector<float> wf(m_ch * 9), bf(m_ch);
-    for (int c = 0; c < m_ch; ++c) {
-      for (int q = 0; q < 9; ++q) wf[c * 9 + q] = (float)(w[c * 9 + q] * sc[c]);
-      bf[c] = (float)sh[c];
-    }
-    stem_w = dev.upload(wf);
-    stem_b = dev.upload(bf);
-  }
+void ResNet::finalize_blocks(const std::string& pre, const char* sc_conv, const char* sc_bn) {
+  const Folded stem = fold_bn(pre + "conv1.weight", pre + "bn1");
+  stem_w = dev.upload(stem.w);
+  stem_b = dev.upload(stem.b);
   for (RBlock& rb : rblocks) {
     const std::string& p = rb.name;
     if (bottleneck) {
@@ -157,8 +248,9 @@ void Model::Impl::finalize_res_blocks(const std::string& pre, const char* sc_con
   }
 }
 
-void Model::Impl::finalize_resnet() {
-  finalize_res_blocks("", "shortcut.0", "shortcut.1");
+void ResNet::finalize() {
+  if (simam) return finalize_simam();
+  finalize_blocks("", "shortcut.0", "shortcut.1");
   // seg_1 over TSTP stats; reference flatten index s*C*F4 + c*F4 + f, ours f*2C + s*C + c
   const int C4 = rblocks.back().out_planes, F4 = feat_dim / 8;
   const auto& W = P("seg_1.weight");
@@ -192,8 +284,8 @@ void Model::Impl::finalize_resnet() {
   }
 }
 
-void Model::Impl::finalize_simam() {
-  finalize_res_blocks("front.", "downsample.0", "downsample.1");
+void ResNet::finalize_simam() {
+  finalize_blocks("front.", "downsample.0", "downsample.1");
   // reference channel index c*F4 + f of x.reshape(B, C*F, T); ours f*C4 + c (frame rows [T][F][C])
   const int C4 = rblocks.back().out_planes, F4 = feat_dim / 8, CF = C4 * F4;
   auto ref_ch = [&](int k) { return (k % C4) * F4 + k / C4; };
@@ -225,10 +317,18 @@ void Model::Impl::finalize_simam() {
   }
 }
 
-Model::Impl::RShapes Model::Impl::resnet_shapes(int T) const {
-  RShapes r;
+void ResNet::check_forward(int, int T) const {
+  WSP_CHECK(opt.precision == 1, "ResNet runs on the bf16x3 kernels only (precision=1)");
+  WSP_CHECK(!simam || (T + 7) / 8 >= 2, "SimAM-ResNet needs >= 2 frames after the three stride-2 stages");
+}
+
+ResNet::Ws ResNet::ws_layout(int B, int T, float* base) const {
+  struct {
+    size_t big = 0, y1 = 0, y2 = 0, sc = 0;  // floats per utterance
+    int F4 = 0, T4 = 0, C4 = 0;
+  } r;
   int Fi = feat_dim, Ti = T;
-  r.big = (size_t)Fi * Ti * m_ch;
+  r.big = (size_t)Fi * Ti * opt.in_planes;
   for (const RBlock& rb : rblocks) {
     const int Fo = (Fi - 1) / rb.stride + 1, To = (Ti - 1) / rb.stride + 1;
     r.big = std::max(r.big, (size_t)Fo * To * rb.out_planes);
@@ -244,29 +344,10 @@ Model::Impl::RShapes Model::Impl::resnet_shapes(int T) const {
   r.F4 = Fi;
   r.T4 = Ti;
   r.C4 = rblocks.back().out_planes;
-  return r;
-}
-
-// utterances per forward chunk: the widest activation operand of any block
-int Model::Impl::resnet_chunk(int B, int T) const {
-  const RShapes r = resnet_shapes(T);
-  return chunk_for(B, std::max(r.big, std::max(r.y1, std::max(r.y2, r.sc))) * sizeof(float));
-}
-
-namespace {
-// one chunk's regions; y1_floats / y2_floats: the (padded) sizes of Y1 / Y2, which the heads reuse
-// as split-K scratch.  From `part` on: SimAM-ResNet only.
-struct ResWs {
-  float *X, *O, *Y1, *Y2, *SC, *pooled;
-  double* part = nullptr;  // f64 moment partials
-  float *coef = nullptr, *Xt = nullptr, *att = nullptr, *logit = nullptr;
-  size_t y1_floats, y2_floats, floats;
-};
-ResWs res_ws(const Model::Impl& m, int B, int T, float* base) {
-  const size_t bc = m.resnet_chunk(B, T);
-  const Model::Impl::RShapes r = m.resnet_shapes(T);
   WsCursor c{base};
-  ResWs w;
+  Ws w;
+  w.bc = chunk_for(B, std::max(r.big, std::max(r.y1, std::max(r.y2, r.sc))) * sizeof(float));
+  const size_t bc = w.bc;
   w.X = c.take(bc * r.big);
   w.O = c.take(bc * r.big);
   w.Y1 = c.take(bc * r.y1);
@@ -275,8 +356,8 @@ ResWs res_ws(const Model::Impl& m, int B, int T, float* base) {
   w.pooled = c.take(bc * r.F4 * 2 * r.C4);
   w.y1_floats = WsCursor::padded(bc * r.y1);
   w.y2_floats = WsCursor::padded(bc * r.y2);
-  if (m.simam) {
-    const size_t CF = (size_t)r.C4 * r.F4, cmax = (size_t)m.rblocks.back().out_planes;
+  if (simam) {
+    const size_t CF = (size_t)r.C4 * r.F4, cmax = (size_t)rblocks.back().out_planes;
     const size_t nchunk = (size_t)std::max(1, ceil_div(2048, (int)bc));
     w.part = reinterpret_cast<double*>(c.take(bc * nchunk * 2 * cmax * 2));
     w.coef = c.take(bc * 2 * cmax);    // mean / 1/(4(v+l))
@@ -287,11 +368,8 @@ ResWs res_ws(const Model::Impl& m, int B, int T, float* base) {
   w.floats = c.off;
   return w;
 }
-}  // namespace
 
-size_t Model::Impl::resnet_ws_floats(int B, int T) const { return res_ws(*this, B, T, nullptr).floats; }
-
-void Model::Impl::gemm2d(const char* tag, const ConvW& cw, const float* a0, int lda, float* out, int ldo, int B, int Fi,
+void ResNet::gemm2d(const char* tag, const ConvW& cw, const float* a0, int lda, float* out, int ldo, int B, int Fi,
                          int Ti, int kw, int stride, int pad, int act, const float* res, int ldres, hipStream_t s) {
   ConvGemmArgs g{};
   one_operand(g, a0, lda, cw.cin);
@@ -307,24 +385,24 @@ void Model::Impl::gemm2d(const char* tag, const ConvW& cw, const float* a0, int 
   g.kw = kw;
   g.res = res;
   g.ldres = ldres;
-  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, x3_variant, s); });
+  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, opt.x3_variant, s); });
 }
 
-void Model::Impl::gemm1x1(const char* tag, const ConvW& cw, const float* a0, float* out, int M, int act,
+void ResNet::gemm1x1(const char* tag, const ConvW& cw, const float* a0, float* out, int M, int act,
                           const float* res, hipStream_t s) {
   ConvGemmArgs g{};
   one_operand(g, a0, cw.cin, cw.cin);
   fill(g, cw, M, M, 1, 0, out, cw.N, act, nullptr, true, nullptr, 0);
   g.res = res;
   g.ldres = cw.N;
-  g.role = res && res_prefetch ? 2 : 0;
-  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, x3_variant, s); });
+  g.role = res && opt.res_prefetch ? 2 : 0;
+  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, opt.x3_variant, s); });
 }
 
 // bottleneck conv3 + projection shortcut as one GEMM (RBlock::c3sc, ConvGemmArgs::sc2d): A segment 0
 // = y2 [M][planes] (row m), segment 1 = the block input x [B][Fi][Ti][Ci] at the shortcut's
 // strided position of output row m
-void Model::Impl::gemm_c3sc(const char* tag, const RBlock& rb, const float* y2, const float* x, int Ci, float* out,
+void ResNet::gemm_c3sc(const char* tag, const RBlock& rb, const float* y2, const float* x, int Ci, float* out,
                             int B, int Fi, int Ti, int Fo, int To, hipStream_t s) {
   const ConvW& cw = rb.c3sc;
   ConvGemmArgs g{};
@@ -343,30 +421,31 @@ void Model::Impl::gemm_c3sc(const char* tag, const RBlock& rb, const float* y2, 
   g.Fo = Fo;
   g.To = To;
   g.stride = rb.stride;
-  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, x3_variant, s); });
+  run(tag, 2.0 * M * cw.N * cw.K, s, [&] { launch_conv_gemm_x3(g, cw.whi, cw.wlo, opt.x3_variant, s); });
 }
 
 // BN-folded 3x3 conv, pad 1, N = cw.N output channels (+ res, then ReLU if relu): the image kernel
 // (conv3x3_img.hip) for a stride-1 conv it supports (img_ok), else the implicit GEMM
-void Model::Impl::conv3x3(const char* tag, const ConvW& cw, const float* in, int ldin, float* out, int B, int Fi,
+void ResNet::conv3x3(const char* tag, const ConvW& cw, const float* in, int ldin, float* out, int B, int Fi,
                           int Ti, int stride, bool relu, const float* res, hipStream_t s) {
   if (stride == 1 && img_ok(cw, cw.N)) {
-    const Conv3x3Args a{in, out, B, Fi, Ti, cw.frag, cw.bias, cw.scale, cw.shift, res, relu, conv3x3_img_on};
+    const Conv3x3Args a{in, out, B, Fi, Ti, cw.frag, cw.bias, cw.scale, cw.shift, res, relu, opt.conv3x3_img};
     run(tag, 2.0 * B * Fi * Ti * cw.N * cw.K, s, [&] { launch_conv3x3_img(a, cw.N, s); });
   } else {
     gemm2d(tag, cw, in, ldin, out, cw.N, B, Fi, Ti, 3, stride, 1, relu ? kActRelu : kActNone, res, res ? cw.N : 0, s);
   }
 }
 
-void Model::Impl::forward_resnet(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
-  const int bc = resnet_chunk(B, T);
-  const ResWs W = res_ws(*this, B, T, ws);
+void ResNet::forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
+  if (simam) return forward_simam(feats, B, T, embed, ws, s);
+  const Ws W = ws_layout(B, T, ws);
+  const int bc = W.bc;
   float *Y1 = W.Y1, *Y2 = W.Y2;
   for (int b0 = 0; b0 < B; b0 += bc) {
     const int nb = std::min(bc, B - b0);
-    int Fi = feat_dim, Ti = T, Ci = m_ch;
+    int Fi = feat_dim, Ti = T, Ci = opt.in_planes;
     run("stem", 0, s, [&] {
-      launch_resnet_stem(feats + (size_t)b0 * T * feat_dim, nb, T, feat_dim, m_ch, stem_w, stem_b, W.X, s);
+      launch_resnet_stem(feats + (size_t)b0 * T * feat_dim, nb, T, feat_dim, opt.in_planes, stem_w, stem_b, W.X, s);
     });
     float* x = W.X;
     float* o = W.O;
@@ -384,19 +463,19 @@ void Model::Impl::forward_resnet(const float* feats, int B, int T, float* embed,
       const int li = rb.li;
       const int Fo = (Fi - 1) / rb.stride + 1, To = (Ti - 1) / rb.stride + 1;
       const float* res = x;
-      const bool tail = bottleneck && rb.stride == 1 && res_tail && rb.w3acc && img_ok(rb.c2, rb.planes);
+      const bool tail = bottleneck && rb.stride == 1 && opt.res_tail && rb.w3acc && img_ok(rb.c2, rb.planes);
       const RBlock* nx = ib + 1 < rblocks.size() ? &rblocks[ib + 1] : nullptr;
       // the tail also runs the next block's conv1 on this block's output (res_tail 1; the next
       // block's conv2 reads y1 from either buffer); at a stage transition the next (first)
       // block's conv1 is 4C -> 2C at this stage's resolution (option c1_stage_fuse)
       const bool fuse1 =
-          tail && res_tail == 1 && nx && nx->w1frag &&
+          tail && opt.res_tail == 1 && nx && nx->w1frag &&
           ((nx->planes == rb.planes && nx->w3acc && nx->stride == 1 && img_ok(nx->c2, nx->planes)) ||
-           (c1_stage_fuse && nx->planes == 2 * rb.planes && nx->in_planes == rb.out_planes && rb.planes <= 64));
+           (opt.c1_stage_fuse && nx->planes == 2 * rb.planes && nx->in_planes == rb.out_planes && rb.planes <= 64));
       // conv3 + shortcut in one GEMM on the non-tail path (sc_fuse): no SC round trip through HBM
-      const bool fuse_sc = bottleneck && rb.has_sc && !tail && (sc_fuse & 1) && rb.c3sc.w && x3_variant == 7;
+      const bool fuse_sc = bottleneck && rb.has_sc && !tail && (opt.sc_fuse & 1) && rb.c3sc.w && opt.x3_variant == 7;
       // ... and inside the tail's conv3 for a stride-1 first block of 32 planes (w3scx)
-      const bool tail_sc = fuse1 && (sc_fuse & 2) && rb.w3scx && nx->planes == rb.planes;
+      const bool tail_sc = fuse1 && (opt.sc_fuse & 2) && rb.w3scx && nx->planes == rb.planes;
       if (rb.has_sc && !fuse_sc && !tail_sc) {
         gemm2d("shortcut", rb.sc, x, Ci, W.SC, rb.out_planes, nb, Fi, Ti, 1, rb.stride, 0, kActNone, nullptr, 0, s);
         res = W.SC;
@@ -466,15 +545,15 @@ void Model::Impl::forward_resnet(const float* feats, int B, int T, float* embed,
   }
 }
 
-void Model::Impl::forward_simam(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
-  const int bc = resnet_chunk(B, T);
-  const ResWs W = res_ws(*this, B, T, ws);
+void ResNet::forward_simam(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
+  const Ws W = ws_layout(B, T, ws);
+  const int bc = W.bc;
   float *Y1 = W.Y1, *Z = W.Y2, *Xt = W.Xt;
   for (int b0 = 0; b0 < B; b0 += bc) {
     const int nb = std::min(bc, B - b0);
-    int Fi = feat_dim, Ti = T, Ci = m_ch;
+    int Fi = feat_dim, Ti = T, Ci = opt.in_planes;
     run("stem", 0, s, [&] {
-      launch_resnet_stem(feats + (size_t)b0 * T * feat_dim, nb, T, feat_dim, m_ch, stem_w, stem_b, W.X, s);
+      launch_resnet_stem(feats + (size_t)b0 * T * feat_dim, nb, T, feat_dim, opt.in_planes, stem_w, stem_b, W.X, s);
     });
     float* x = W.X;
     float* o = W.O;

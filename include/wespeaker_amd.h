@@ -131,7 +131,9 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
 /* arch: "ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
  * "ECAPA_TDNN_GLOB_c1024", "ResNet18/34/50/101/152/221/293",
  * "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP", "CAMPPlus" (CAM++: feat_dim a
- * multiple of 8, TSTP pooling, no emb_bn / two_emb_layer, >= 3 frames)
+ * multiple of 8, TSTP pooling, no emb_bn / two_emb_layer, >= 3 frames),
+ * "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug" (feat_dim a multiple
+ * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames)
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
  * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
  * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /

@@ -80,6 +80,39 @@ static void test_frag(int N, int K, FragOrder order, int kacc) {
   check_frag(what, pk.data(), N, K, acc_below, [&](int n, int k) { return w[(size_t)n * K + k]; });
 }
 
+// frag16 image [Kp/32][2][Np/16][64][8] of a [N][K] window (row stride ldw): every (n, k) in its
+// slot, every padding slot zero
+static void test_frag16(int N, int K, int ldw, bool acc) {
+  std::vector<float> w((size_t)N * ldw);
+  for (size_t i = 0; i < w.size(); ++i) w[i] = value(i);
+  const std::vector<uint16_t> pk = frag16(w.data(), N, K, ldw, acc);
+  const int NT = (N + 15) / 16, KS = (K + 31) / 32;
+  const size_t total = (size_t)KS * 2 * NT * 64 * 8;
+  char what[64];
+  std::snprintf(what, sizeof what, "frag16 %dx%d ld %d acc %d", N, K, ldw, (int)acc);
+  CHECK(pk.size() == total, "%s: %zu halves", what, pk.size());
+  if (pk.size() != total) return;
+  std::vector<int> seen(total, 0);
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k) {
+      const int ks = k / 32, r = k % 32;
+      // plain: r = 8 q + e; acc: r = 16 (e >> 2) + 4 q + (e & 3)
+      const int q = acc ? (r >> 2) & 3 : r >> 3, e = acc ? 4 * (r >> 4) + (r & 3) : r & 7;
+      const size_t hi_at = ((((size_t)ks * 2 + 0) * NT + n / 16) * 64 + (n % 16) + 16 * q) * 8 + e;
+      const size_t lo_at = hi_at + (size_t)NT * 64 * 8;
+      const float v = w[(size_t)n * ldw + k];
+      const uint16_t hi = f2bf(v), lo = f2bf(v - bf2f(hi));
+      CHECK(pk[hi_at] == hi, "%s hi plane n=%d k=%d: %04x != %04x", what, n, k, pk[hi_at], hi);
+      CHECK(pk[lo_at] == lo, "%s lo plane n=%d k=%d: %04x != %04x", what, n, k, pk[lo_at], lo);
+      ++seen[hi_at];
+      ++seen[lo_at];
+    }
+  for (size_t i = 0; i < total; ++i) {
+    CHECK(seen[i] <= 1, "%s slot %zu is the target of %d elements", what, i, seen[i]);
+    if (!seen[i]) CHECK(pk[i] == 0, "%s padding slot %zu holds %04x", what, i, pk[i]);
+  }
+}
+
 static void test_res2(int w) {
   std::vector<float> W[7];
   const std::vector<float>* Wp[7];
@@ -171,6 +204,11 @@ int main() {
   test_frag(64, 48, kPlain, -1);
   test_frag(128, 64, kAcc, -1);
   test_frag(128, 64, kAcc, 32);
+  test_frag16(16, 144, 144, false);  // K padded to 160
+  test_frag16(24, 216, 216, false);  // N padded to 32, K to 224
+  test_frag16(72, 64, 80, false);    // a window of wider rows, N padded to 80
+  test_frag16(64, 32, 32, true);
+  test_frag16(96, 64, 70, true);
   test_res2(32);
   test_res2(64);
   if (g_fail) {

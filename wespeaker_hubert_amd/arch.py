@@ -43,6 +43,14 @@ CAMPP_ARCHS = {
 }
 CAMPP_SEG = 100  # CAMLayer.seg_pooling's segment length
 
+ERES2NET_ARCHS = {
+    # name: (m_channels, baseWidth, scale, expansion) — eres2net.py:394-430, num_blocks (3, 4, 6, 3)
+    "ERes2Net34_Base": (32, 32, 2, 2),
+    "ERes2Net34_Large": (64, 32, 2, 2),
+    "ERes2Net34_aug": (64, 24, 3, 4),
+}
+ERES2NET_BLOCKS = (3, 4, 6, 3)
+
 
 @dataclass
 class ModelSpec:
@@ -65,6 +73,8 @@ class ModelSpec:
             return "simam"
         if self.arch in CAMPP_ARCHS:
             return "campplus"
+        if self.arch in ERES2NET_ARCHS:
+            return "eres2net"
         raise KeyError(self.arch)
 
 
@@ -73,10 +83,22 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
 
     Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57).
     """
-    if arch not in ECAPA_ARCHS and arch not in RESNET_ARCHS and arch not in SIMAM_ARCHS and arch not in CAMPP_ARCHS:
-        raise KeyError(f"{arch} not found !!! (supported: "
-                       f"{sorted(ECAPA_ARCHS) + sorted(RESNET_ARCHS) + sorted(SIMAM_ARCHS) + sorted(CAMPP_ARCHS)})")
+    known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS)
+    if not any(arch in k for k in known):
+        raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
     kw = dict(model_args)
+    if arch in ERES2NET_ARCHS:
+        # ERes2Net34_*(feat_dim, embed_dim, pooling_func='TSTP', two_emb_layer=False)
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 192)),
+                         pooling_func=kw.pop("pooling_func", "TSTP"),
+                         two_emb_layer=bool(kw.pop("two_emb_layer", False)), m_channels=ERES2NET_ARCHS[arch][0])
+        if spec.pooling_func != "TSTP":
+            raise NotImplementedError("ERes2Net path implements TSTP pooling (the recipe configuration)")
+        if spec.feat_dim < 8 or spec.feat_dim % 8:
+            # eres2net.py:261 sizes seg_1 for int(feat_dim / 8) rows while stage 4 keeps ceil(feat_dim / 8)
+            raise ValueError("ERes2Net feat_dim must be a positive multiple of 8")
+        spec.extra = kw
+        return spec
     if arch in CAMPP_ARCHS:
         # CAMPPlus(feat_dim=80, embed_dim=512, pooling_func='TSTP', growth_rate=32, bn_size=4,
         #          init_channels=128, config_str='batchnorm-relu')
@@ -237,9 +259,65 @@ def campplus_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def eres2net_blocks(spec: ModelSpec):
+    """(prefix, in_planes, planes, width, stride, aff, has_shortcut) of every block (eres2net.py:106-352)."""
+    m, base_width, scale, exp = ERES2NET_ARCHS[spec.arch]
+    in_planes = m
+    for li, n in enumerate(ERES2NET_BLOCKS):
+        planes = m * (2 ** li)
+        width = int(planes * base_width // 64)
+        for bi in range(n):
+            stride = 2 if (li > 0 and bi == 0) else 1
+            yield (f"layer{li + 1}.{bi}", in_planes, planes, width, stride, li >= 2,
+                   stride != 1 or in_planes != exp * planes)
+            in_planes = exp * planes
+
+
+def _aff(p: str, c: int) -> ParamList:
+    h = c // 4
+    return ([(p + ".local_att.0.weight", (h, 2 * c, 1, 1)), (p + ".local_att.0.bias", (h,))] + _bn(p + ".local_att.1", h)
+            + [(p + ".local_att.3.weight", (c, h, 1, 1)), (p + ".local_att.3.bias", (c,))] + _bn(p + ".local_att.4", c))
+
+
+def eres2net_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of ERes2Net (eres2net.py:75-335): stem, the Res2 blocks (stages 3-4 with an
+    AFF in front of every 3x3 conv but the first), the bottom-up downsample convs and AFFs, seg_1."""
+    m, _, scale, exp = ERES2NET_ARCHS[spec.arch]
+    out: ParamList = [("conv1.weight", (m, 1, 3, 3))] + _bn("bn1", m)
+    for p, in_planes, planes, w, stride, aff, has_sc in eres2net_blocks(spec):
+        out += [(p + ".conv1.weight", (w * scale, in_planes, 1, 1))] + _bn(p + ".bn1", w * scale)
+        if aff:
+            out += [(p + ".conv2_1.weight", (w, w, 3, 3))] + _bn(p + ".bn2_1", w)
+            out += [(f"{p}.convs.{i}.weight", (w, w, 3, 3)) for i in range(scale - 1)]
+            for i in range(scale - 1):
+                out += _bn(f"{p}.bns.{i}", w)
+            for i in range(scale - 1):
+                out += _aff(f"{p}.fuse_models.{i}", w)
+        else:
+            out += [(f"{p}.convs.{i}.weight", (w, w, 3, 3)) for i in range(scale)]
+            for i in range(scale):
+                out += _bn(f"{p}.bns.{i}", w)
+        out += [(p + ".conv3.weight", (planes * exp, w * scale, 1, 1))] + _bn(p + ".bn3", planes * exp)
+        if has_sc:
+            out += [(p + ".shortcut.0.weight", (planes * exp, in_planes, 1, 1))] + _bn(p + ".shortcut.1", planes * exp)
+    c = m * exp
+    out += [(f"layer{i}_downsample.weight", (c * 2 ** i, c * 2 ** (i - 1), 3, 3)) for i in (1, 2, 3)]
+    for i, name in enumerate(("fuse_mode12", "fuse_mode123", "fuse_mode1234"), 1):
+        out += _aff(name, c * 2 ** i)
+    stats_dim = int(spec.feat_dim / 8) * m * 8 * exp
+    out += [("seg_1.weight", (spec.embed_dim, stats_dim * 2)), ("seg_1.bias", (spec.embed_dim,))]
+    if spec.two_emb_layer:
+        out += [("seg_bn_1.running_mean", (spec.embed_dim,)), ("seg_bn_1.running_var", (spec.embed_dim,)),
+                ("seg_bn_1.num_batches_tracked", ()),
+                ("seg_2.weight", (spec.embed_dim, spec.embed_dim)), ("seg_2.bias", (spec.embed_dim,))]
+    return out
+
+
 def param_list(spec: ModelSpec) -> ParamList:
     if spec.family == "campplus":
         return campplus_params(spec)
+    if spec.family == "eres2net":
+        return eres2net_params(spec)
     if spec.family == "ecapa":
         return ecapa_params(spec)
     if spec.family == "simam":
@@ -289,6 +367,30 @@ def campplus_gflop_per_utt(spec: ModelSpec, T: int) -> float:
         macs += t * ch * (ch // 2)
         ch //= 2
     macs += 2 * ch * spec.embed_dim
+    return 2.0 * macs / 1e9
+
+
+def eres2net_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one ERes2Net forward over T frames: stem, every block's 1x1 and
+    3x3 convs, its AFFs (2C -> C/4 -> C), shortcuts, the bottom-up downsample convs and AFFs, seg_1."""
+    m, _, scale, exp = ERES2NET_ARCHS[spec.arch]
+    F, t = spec.feat_dim, T
+    macs = F * t * m * 9
+    pos = {}
+    for p, in_planes, planes, w, stride, aff, has_sc in eres2net_blocks(spec):
+        F, t = (F - 1) // stride + 1, (t - 1) // stride + 1
+        n = F * t
+        macs += n * (in_planes * w * scale + scale * 9 * w * w + w * scale * planes * exp)
+        if aff:
+            macs += n * (scale - 1) * (2 * w * (w // 4) + (w // 4) * w)
+        if has_sc:
+            macs += n * in_planes * planes * exp
+        pos[p.split(".")[0]] = n
+    c = m * exp
+    for i in (1, 2, 3):
+        ci, co, n = c * 2 ** (i - 1), c * 2 ** i, pos[f"layer{i + 1}"]
+        macs += n * (9 * ci * co + 2 * co * (co // 4) + (co // 4) * co)
+    macs += 2 * c * 8 * F * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
     return 2.0 * macs / 1e9
 
 

@@ -4,6 +4,7 @@
 // state, defined in its own translation unit (source map and "adding a family"):
 //   ecapa_model.cpp   Ecapa     resnet_model.cpp    ResNet (and SimAM-ResNet)
 //   hubert_model.cpp  Hubert    campplus_model.cpp  Campplus
+//   eres2net_model.cpp  Eres2Net
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -252,6 +253,6 @@ struct Model::Impl {
 // One per family, defined beside its subclass: the arch names the family serves, their argument
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
-MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus;
+MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net;
 
 }  // namespace wsp

@@ -53,6 +53,25 @@ std::vector<uint16_t> frag(const std::vector<float>& w, int N, int K, FragOrder 
   return pk;
 }
 
+std::vector<uint16_t> frag16(const float* w, int N, int K, int ldw, bool acc_order) {
+  const int NT = (N + 15) / 16, KS = (K + 31) / 32;
+  std::vector<uint16_t> pk((size_t)KS * 2 * NT * 64 * 8, 0);
+  for (int ks = 0; ks < KS; ++ks)
+    for (int jt = 0; jt < NT; ++jt)
+      for (int l = 0; l < 64; ++l)
+        for (int e = 0; e < 8; ++e) {
+          const int n = 16 * jt + (l & 15);
+          const int k = 32 * ks + (acc_order ? 16 * (e >> 2) + 4 * (l >> 4) + (e & 3) : 8 * (l >> 4) + e);
+          if (n >= N || k >= K) continue;
+          const float v = w[(size_t)n * ldw + k];
+          const uint16_t hi = f2bf(v);
+          const size_t o = (((size_t)ks * 2 * NT + jt) * 64 + l) * 8 + e;
+          pk[o] = hi;
+          pk[o + (size_t)NT * 64 * 8] = f2bf(v - bf2f(hi));
+        }
+  return pk;
+}
+
 std::vector<uint16_t> frag_res2(const std::vector<float>* const W[7], int w) {
   const size_t per = (size_t)(3 * w / 16) * 2 * (w / 32) * 64 * 8;
   std::vector<uint16_t> pk(7 * per);

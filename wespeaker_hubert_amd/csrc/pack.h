@@ -44,6 +44,15 @@ std::vector<float> transpose(const float* w, int N, int K, int ldk);
 enum FragOrder { kPlain, kAcc };
 std::vector<uint16_t> frag(const std::vector<float>& w, int N, int K, FragOrder order = kPlain, int kacc = -1);
 
+// Weight [N][K] (row stride ldw) -> bf16 hi / lo operand fragments of 16x16x32 MFMAs, rows padded
+// with zeros to Np = round_up(N, 16) and k to Kp = round_up(K, 32):
+// [Kp/32 k-steps][2 planes][Np/16 tiles][64 lanes][8].  Lane l, element e of k-step ks and tile j
+// holds W[16 j + (l & 15)][k], k = 32 ks + 8 (l >> 4) + e or, acc_order,
+// k = 32 ks + 16 (e >> 2) + 4 (l >> 4) + (e & 3): the order in which two stacked 16x16 accumulator
+// tiles (register r = row 4 (l >> 4) + r) hold their 32 rows, so such accumulators are the other
+// operand of this weight's MFMAs without a shuffle (eres2net.hip, the AFF's second product)
+std::vector<uint16_t> frag16(const float* w, int N, int K, int ldw, bool acc_order = false);
+
 // Res2Net chain (res2_chain.hip): 7 conv weights W_i [w][w][3] -> [7] plain fragment images of
 // [w][3w] with k = tap * w + c
 std::vector<uint16_t> frag_res2(const std::vector<float>* const W[7], int w);

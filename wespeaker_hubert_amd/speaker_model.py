@@ -184,7 +184,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -260,7 +260,8 @@ class HipSpeakerModel(_HipHandle):
     def __call__(self, feats: torch.Tensor):
         # SimAM_ResNet*_ASP.forward and CAMPPlus.forward return the embedding itself
         # (samresnet.py:135-143, campplus.py:409-413); ECAPA / ResNet return (aux, embed)
-        if self.spec.family in ("simam", "campplus"):
+        # as does ERes2Net.forward (eres2net.py:380-391)
+        if self.spec.family in ("simam", "campplus", "eres2net"):
             return self.embed(feats)
         return None, self.embed(feats)
 

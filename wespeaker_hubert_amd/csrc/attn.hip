@@ -542,7 +542,8 @@ __global__ __launch_bounds__(256) void attn_gate_kernel(const float* __restrict_
 void launch_attn(const float* qkv, int ldq, float* out, int ldo, int B, int T, int H, int dh, hipStream_t s,
                  const int* seg, int pipe, const AttnBias* bias) {
   WSP_CHECK(dh == kDh, "attn: head dim must be 64");
-  WSP_CHECK(B > 0 && T > 0 && H > 0 && ldq >= 3 * H * dh && ldq % 4 == 0 && ldo % 4 == 0, "attn: bad shape");
+  WSP_CHECK(B > 0 && T > 0 && H > 0 && ldq >= 3 * H * dh && ldq % 4 == 0 && ldo >= H * dh && ldo % 4 == 0,
+            "attn: bad shape");
   WSP_CHECK(!bias || (bias->table && bias->gate), "attn: bias needs its table and gate");
   const float* nul = nullptr;
   if (pipe) {

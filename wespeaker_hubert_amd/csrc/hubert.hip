@@ -300,8 +300,10 @@ size_t hubert_conv0_stats_doubles(int B, int T0) { return (size_t)B * ((T0 + kMT
 
 void launch_layernorm(const LayerNormArgs& p, hipStream_t s) {
   WSP_CHECK(p.M > 0 && (p.D == 512 || p.D == 768), "layernorm: D must be 512 or 768");
-  WSP_CHECK(!p.add || (p.gin > 0 && p.gout >= p.gin && p.gin % 4 == 0 && p.gout % 4 == 0 && p.ldadd % 4 == 0),
+  WSP_CHECK(!p.add || (p.gin > 0 && p.gout >= p.gin && p.gin % 4 == 0 && p.gout % 4 == 0 && p.ldadd % 4 == 0 &&
+                       (p.D - 1) / p.gin * p.gout + p.gin <= p.ldadd),  // the last group's run ends inside a row
             "layernorm: bad add remap");
+  WSP_CHECK(p.ldx >= p.D && p.ldo >= p.D, "layernorm: rows narrower than D");
   WSP_CHECK(p.ldx % 4 == 0 && p.ldo % 4 == 0, "layernorm: rows must be 16-B aligned");
   WSP_CHECK(!p.feat || p.seg || (p.T > 0 && p.Tout > 0 && p.M % p.T == 0), "layernorm: bad featurizer shape");
   WSP_CHECK(!p.seg || (p.fseg && p.nseg > 0), "layernorm: segmented featurizer needs output offsets");

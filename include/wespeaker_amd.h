@@ -133,7 +133,9 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
  * "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP", "CAMPPlus" (CAM++: feat_dim a
  * multiple of 8, TSTP pooling, no emb_bn / two_emb_layer, >= 3 frames),
  * "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug" (feat_dim a multiple
- * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames)
+ * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames),
+ * "Gemini_DF_ResNet60/114/183/237" (feat_dim a multiple of 16, TSTP pooling,
+ * two_emb_layer optional, no emb_bn, >= 3 frames)
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
  * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
  * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /
@@ -218,6 +220,11 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *   "cam_fused"    CAMPPlus: 1 (default) = the dense layers' BatchNorm + ReLU inside the 1x1
  *                  GEMM's A prologue; 0 = an elementwise pass of its own into scratch (A/B
  *                  runs only; bit-identical)
+ *   "ib_fused"     Gemini DF-ResNet: 0 (default) = an inverted bottleneck runs as conv1, depthwise
+ *                  3x3, conv3 + residual (three launches); 1 = conv1, then one launch that forms the
+ *                  depthwise conv's output inside conv3's operand (no 4d-wide intermediate; slower
+ *                  as measured, kept for A/B runs).  Equal up to fp32 rounding; the workspace
+ *                  follows the value, so query its size after setting it
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block

@@ -51,6 +51,16 @@ ERES2NET_ARCHS = {
 }
 ERES2NET_BLOCKS = (3, 4, 6, 3)
 
+GEMINI_ARCHS = {
+    # name: depths — gemini_dfresnet.py:145-178 (the downsample layers count as layers)
+    "Gemini_DF_ResNet60": (3, 3, 9, 3),
+    "Gemini_DF_ResNet114": (3, 3, 27, 3),
+    "Gemini_DF_ResNet183": (3, 8, 45, 3),
+    "Gemini_DF_ResNet237": (3, 8, 63, 3),
+}
+GEMINI_DIMS = (32, 32, 64, 128, 256)
+GEMINI_STRIDE_T = (1, 2, 1, 1)  # Golden Gemini T14c: the frequency stride is 2 at every level
+
 
 @dataclass
 class ModelSpec:
@@ -75,18 +85,35 @@ class ModelSpec:
             return "campplus"
         if self.arch in ERES2NET_ARCHS:
             return "eres2net"
+        if self.arch in GEMINI_ARCHS:
+            return "gemini"
         raise KeyError(self.arch)
 
 
-def make_spec(arch: str, **model_args) -> ModelSpec:
-    """`get_speaker_model(arch)(**model_args)` analogue (speaker_model.py:30-57).
-
-    Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57).
-    """
-    known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS)
+def check_arch(arch: str) -> None:
+    """Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57)."""
+    known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS)
     if not any(arch in k for k in known):
         raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
+
+
+def make_spec(arch: str, **model_args) -> ModelSpec:
+    """`get_speaker_model(arch)(**model_args)` analogue (speaker_model.py:30-57)."""
+    check_arch(arch)
     kw = dict(model_args)
+    if arch in GEMINI_ARCHS:
+        # Gemini_DF_ResNet*(feat_dim, embed_dim, pooling_func='TSTP', two_emb_layer=False); the class
+        # defaults are feat_dim 40 / embed_dim 128 (gemini_dfresnet.py:53-59)
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 40)), embed_dim=int(kw.pop("embed_dim", 128)),
+                         pooling_func=kw.pop("pooling_func", "TSTP"),
+                         two_emb_layer=bool(kw.pop("two_emb_layer", False)))
+        if spec.pooling_func != "TSTP":
+            raise NotImplementedError("Gemini DF-ResNet path implements TSTP pooling (the recipe configuration)")
+        if spec.feat_dim < 16 or spec.feat_dim % 16:
+            # gemini_dfresnet.py:63 sizes seg_1 for int(feat_dim / 16) rows while level 4 keeps ceil(feat_dim / 16)
+            raise ValueError("Gemini DF-ResNet feat_dim must be a positive multiple of 16")
+        spec.extra = kw
+        return spec
     if arch in ERES2NET_ARCHS:
         # ERes2Net34_*(feat_dim, embed_dim, pooling_func='TSTP', two_emb_layer=False)
         spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 192)),
@@ -313,7 +340,32 @@ def eres2net_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def gemini_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of Gemini_DF_ResNet (gemini_dfresnet.py:51-103): every downsample layer (0 is
+    the stem) first, then the inverted bottlenecks stage by stage, then seg_1."""
+    dims = GEMINI_DIMS
+    out: ParamList = [("downsample_layers.0.0.weight", (dims[0], 1, 3, 3))] + _bn("downsample_layers.0.1", dims[0])
+    for i in range(1, 5):
+        out += [(f"downsample_layers.{i}.0.weight", (dims[i], dims[i - 1], 3, 3))] + _bn(f"downsample_layers.{i}.1", dims[i])
+    for li, n in enumerate(GEMINI_ARCHS[spec.arch]):
+        d = dims[li + 1]
+        for bi in range(n):
+            p = f"stages.{li}.{bi}"
+            out += [(p + ".conv1.weight", (4 * d, d, 1, 1))] + _bn(p + ".bn1", 4 * d)
+            out += [(p + ".conv2.weight", (4 * d, 1, 3, 3))] + _bn(p + ".bn2", 4 * d)
+            out += [(p + ".conv3.weight", (d, 4 * d, 1, 1))] + _bn(p + ".bn3", d)
+    stats_dim = int(spec.feat_dim / 16) * dims[4]
+    out += [("seg_1.weight", (spec.embed_dim, stats_dim * 2)), ("seg_1.bias", (spec.embed_dim,))]
+    if spec.two_emb_layer:
+        out += [("seg_bn_1.running_mean", (spec.embed_dim,)), ("seg_bn_1.running_var", (spec.embed_dim,)),
+                ("seg_bn_1.num_batches_tracked", ()),
+                ("seg_2.weight", (spec.embed_dim, spec.embed_dim)), ("seg_2.bias", (spec.embed_dim,))]
+    return out
+
+
 def param_list(spec: ModelSpec) -> ParamList:
+    if spec.family == "gemini":
+        return gemini_params(spec)
     if spec.family == "campplus":
         return campplus_params(spec)
     if spec.family == "eres2net":
@@ -391,6 +443,21 @@ def eres2net_gflop_per_utt(spec: ModelSpec, T: int) -> float:
         ci, co, n = c * 2 ** (i - 1), c * 2 ** i, pos[f"layer{i + 1}"]
         macs += n * (9 * ci * co + 2 * co * (co // 4) + (co // 4) * co)
     macs += 2 * c * 8 * F * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
+    return 2.0 * macs / 1e9
+
+
+def gemini_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one Gemini DF-ResNet forward over T frames, convolutions only:
+    the stem, per level the downsample conv and its inverted bottlenecks (two 1x1 convs of 4 d^2 and
+    the depthwise 3x3 of 36 d MACs per position), seg_1."""
+    dims = GEMINI_DIMS
+    F, t = spec.feat_dim, T
+    macs = F * t * dims[0] * 9
+    for li, n in enumerate(GEMINI_ARCHS[spec.arch]):
+        F, t = (F - 1) // 2 + 1, (t - 1) // GEMINI_STRIDE_T[li] + 1
+        d = dims[li + 1]
+        macs += F * t * (9 * dims[li] * d + n * (8 * d * d + 36 * d))
+    macs += 2 * F * dims[4] * spec.embed_dim
     return 2.0 * macs / 1e9
 
 

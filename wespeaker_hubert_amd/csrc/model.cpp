@@ -3,7 +3,7 @@
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
 // The families derive from Model::Impl: their tables, folds, workspace layouts and forward
 // schedules are in ecapa_model.cpp, resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp,
-// campplus_model.cpp and eres2net_model.cpp; Model::create below is the one place here that names them.
+// campplus_model.cpp, eres2net_model.cpp and gemini_model.cpp; Model::create below is the one place here that names them.
 #include "model_impl.h"
 
 namespace wsp {
@@ -175,7 +175,7 @@ Model::~Model() { delete impl; }
 
 void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
   WSP_CHECK(!impl, "model already created");
-  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net})
+  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini})
     if ((impl = make(arch, feat_dim, embed_dim, emb_bn, two_emb))) break;
   WSP_CHECK(impl, "unsupported arch " + arch);
   // Creation and parameter intake are host-only; the device is bound at
@@ -281,6 +281,7 @@ const Opt kOpts[] = {
     {"in_planes", &I::in_planes, 32, 64, kNoHole, "in_planes must be 32 or 64"},  // the two ends only (set_option)
     {"res2_fused", &I::res2_fused, 0, 1, kNoHole, "res2_fused must be 0 or 1"},
     {"cam_fused", &I::cam_fused, 0, 1, kNoHole, "cam_fused must be 0 (separate BN-ReLU pass) or 1 (GEMM prologue)"},
+    {"ib_fused", &I::ib_fused, 0, 1, kNoHole, "ib_fused must be 0 (conv1, depthwise conv, conv3) or 1 (conv1, fused tail)"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
     {"gate_fold", &I::gate_fold, 0, 1, kNoHole, "gate_fold must be 0 or 1"},
     {"res_prefetch", &I::res_prefetch, 0, 1, kNoHole, "res_prefetch must be 0 or 1"},

@@ -4,7 +4,7 @@
 // state, defined in its own translation unit (source map and "adding a family"):
 //   ecapa_model.cpp   Ecapa     resnet_model.cpp    ResNet (and SimAM-ResNet)
 //   hubert_model.cpp  Hubert    campplus_model.cpp  Campplus
-//   eres2net_model.cpp  Eres2Net
+//   eres2net_model.cpp  Eres2Net  gemini_model.cpp  Gemini
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -158,6 +158,10 @@ struct Options {
   // CAM++: 1 = the dense layers' BN-ReLU inside the GEMM's A prologue; 0 = an elementwise pass of
   // its own into scratch (A/B runs only)
   int cam_fused = 1;
+  // Gemini DF-ResNet: 0 = an inverted bottleneck is conv1, depthwise conv, projection as three
+  // launches (the family's default: measured faster); 1 = conv1 + the fused tail (depthwise 3x3
+  // inside the 1x1 projection's operand)
+  int ib_fused = 0;
 };
 
 struct Model::Impl {
@@ -253,6 +257,6 @@ struct Model::Impl {
 // One per family, defined beside its subclass: the arch names the family serves, their argument
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
-MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net;
+MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini;
 
 }  // namespace wsp

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arch import ModelSpec, make_spec, param_list
+from .arch import ModelSpec, check_arch, make_spec, param_list
 
 logger = logging.getLogger(__name__)
 
@@ -184,7 +184,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Gemini DF-ResNet speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -260,7 +260,8 @@ class HipSpeakerModel(_HipHandle):
     def __call__(self, feats: torch.Tensor):
         # SimAM_ResNet*_ASP.forward and CAMPPlus.forward return the embedding itself
         # (samresnet.py:135-143, campplus.py:409-413); ECAPA / ResNet return (aux, embed)
-        # as does ERes2Net.forward (eres2net.py:380-391)
+        # as does ERes2Net.forward (eres2net.py:380-391); Gemini_DF_ResNet.forward returns
+        # (tensor(0.), embed) like ResNet (gemini_dfresnet.py:129-141)
         if self.spec.family in ("simam", "campplus", "eres2net"):
             return self.embed(feats)
         return None, self.embed(feats)
@@ -270,7 +271,7 @@ class HipSpeakerModel(_HipHandle):
 
 def get_speaker_model(model_name: str):
     """speaker_model.py:30-57 — returns a constructor taking **model_args."""
-    make_spec(model_name)  # raises KeyError for unknown names
+    check_arch(model_name)  # raises KeyError for unknown names
 
     def ctor(**model_args):
         return HipSpeakerModel(model_name, **model_args)

@@ -135,7 +135,17 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
  * "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug" (feat_dim a multiple
  * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames),
  * "Gemini_DF_ResNet60/114/183/237" (feat_dim a multiple of 16, TSTP pooling,
- * two_emb_layer optional, no emb_bn, >= 3 frames)
+ * two_emb_layer optional, no emb_bn, >= 3 frames),
+ * "XVEC" (the x-vector TDNN with TSTP pooling, >= 16 frames) and "XI_VEC_XVEC"
+ * (the same TDNN with XI pooling, >= 15 frames): feat_dim a multiple of 4, no
+ * emb_bn / two_emb_layer, the embedding is embed_b; this interface has no pooling
+ * argument, so the name carries it: a host that is given (XVEC, pooling_func XI)
+ * creates "XI_VEC_XVEC" and the reverse; wsp_model_forward_segments sees the
+ * frame offsets only on the device, so its caller must guarantee that minimum for
+ * every utterance of a ragged batch (only the total is checked; a shorter utterance
+ * gets an undefined embedding),
+ * "XI_VEC_ECAPA_TDNN_c512", "XI_VEC_ECAPA_TDNN_c1024" (the ECAPA trunk with XI
+ * pooling and a 1536-wide head; emb_bn optional, no two_emb_layer, >= 1 frame)
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
  * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
  * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /

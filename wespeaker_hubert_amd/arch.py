@@ -61,6 +61,22 @@ GEMINI_ARCHS = {
 GEMINI_DIMS = (32, 32, 64, 128, 256)
 GEMINI_STRIDE_T = (1, 2, 1, 1)  # Golden Gemini T14c: the frequency stride is 2 at every level
 
+XVEC_ARCHS = {
+    # name: default pooling_func — tdnn.py:57-118, xi_vector.py XI_VEC_XVEC
+    "XVEC": "TSTP",
+    "XI_VEC_XVEC": "XI",
+}
+XVEC_HID, XVEC_STATS = 512, 1500
+# (kernel, dilation) of frame_1..5: unpadded convs, T' = T - 14
+XVEC_FRAMES = ((5, 1), (3, 2), (3, 3), (1, 1), (1, 1))
+XVEC_SHRINK = sum((k - 1) * d for k, d in XVEC_FRAMES)
+XI_HIDDEN = 256  # pooling_layers.py class XI: hidden_size 256, stddev False (the constructors cannot change either)
+XI_ECAPA_ARCHS = {
+    # name: channels — xi_vector.py: ECAPA_TDNN(pooling_func='XI'), no global context
+    "XI_VEC_ECAPA_TDNN_c512": 512,
+    "XI_VEC_ECAPA_TDNN_c1024": 1024,
+}
+
 
 @dataclass
 class ModelSpec:
@@ -75,8 +91,10 @@ class ModelSpec:
 
     @property
     def family(self) -> str:
-        if self.arch.startswith("ECAPA_TDNN"):
+        if self.arch.startswith("ECAPA_TDNN") or self.arch in XI_ECAPA_ARCHS:
             return "ecapa"
+        if self.arch in XVEC_ARCHS:
+            return "xvec"
         if self.arch.startswith("ResNet"):
             return "resnet"
         if self.arch.startswith("SimAM_ResNet"):
@@ -92,7 +110,8 @@ class ModelSpec:
 
 def check_arch(arch: str) -> None:
     """Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57)."""
-    known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS)
+    known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS, XVEC_ARCHS,
+             XI_ECAPA_ARCHS)
     if not any(arch in k for k in known):
         raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
 
@@ -101,6 +120,34 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
     """`get_speaker_model(arch)(**model_args)` analogue (speaker_model.py:30-57)."""
     check_arch(arch)
     kw = dict(model_args)
+    if arch in XVEC_ARCHS:
+        # XVEC(feat_dim=40, hid_dim=512, stats_dim=1500, embed_dim=512, pooling_func='TSTP');
+        # XI_VEC_XVEC(feat_dim, embed_dim, pooling_func='XI') builds the same class
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 40)), embed_dim=int(kw.pop("embed_dim", 512)),
+                         pooling_func=kw.pop("pooling_func", XVEC_ARCHS[arch]))
+        if spec.pooling_func not in ("TSTP", "XI"):
+            raise NotImplementedError("XVEC path implements TSTP and XI pooling")
+        for key in ("emb_bn", "two_emb_layer"):  # tdnn.py's constructor has neither (a TypeError there too)
+            if key in kw:
+                raise TypeError(f"XVEC has no {key}")
+        for key, want in (("hid_dim", XVEC_HID), ("stats_dim", XVEC_STATS)):
+            if kw.pop(key, want) != want:
+                raise NotImplementedError(f"XVEC path implements {key}={want} (the recipe configuration)")
+        if spec.feat_dim < 4 or spec.feat_dim % 4:
+            raise ValueError("XVEC feat_dim must be a positive multiple of 4")
+        spec.extra = kw
+        return spec
+    if arch in XI_ECAPA_ARCHS:
+        # XI_VEC_ECAPA_TDNN_c*(feat_dim, embed_dim, pooling_func='XI', emb_bn=False): no defaults in the
+        # reference; the project's ECAPA defaults
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 192)),
+                         pooling_func=kw.pop("pooling_func", "XI"), emb_bn=bool(kw.pop("emb_bn", False)))
+        if spec.pooling_func != "XI":
+            raise NotImplementedError("XI_VEC_ECAPA_TDNN path implements XI pooling (ASTP: the ECAPA_TDNN_* names)")
+        if "two_emb_layer" in kw:  # xi_vector.py's factories do not take it (a TypeError there too)
+            raise TypeError("XI_VEC_ECAPA_TDNN has no two_emb_layer")
+        spec.extra = kw
+        return spec
     if arch in GEMINI_ARCHS:
         # Gemini_DF_ResNet*(feat_dim, embed_dim, pooling_func='TSTP', two_emb_layer=False); the class
         # defaults are feat_dim 40 / embed_dim 128 (gemini_dfresnet.py:53-59)
@@ -168,9 +215,52 @@ def _bn(p: str, c: int) -> ParamList:
             (p + ".running_var", (c,)), (p + ".num_batches_tracked", ())]
 
 
+def xi_params(p: str, dim: int) -> ParamList:
+    """state_dict layout of the XI pooling layer (pooling_layers.py class XI) over `dim` channels."""
+    out: ParamList = [(p + ".prior_mean", (1, dim)), (p + ".prior_logprec", (1, dim)),
+                      (p + ".lin1_relu_bn.0.weight", (XI_HIDDEN, dim, 1)), (p + ".lin1_relu_bn.0.bias", (XI_HIDDEN,))]
+    out += _bn(p + ".lin1_relu_bn.2", XI_HIDDEN)
+    out += [(p + ".lin2.weight", (dim, XI_HIDDEN, 1)), (p + ".lin2.bias", (dim,))]
+    return out
+
+
+def xvec_handle_arch(spec: ModelSpec) -> str:
+    """The library's arch string of an x-vector spec: the C ABI has no pooling argument, so the name
+    carries it (XVEC = TSTP, XI_VEC_XVEC = XI), whichever constructor the caller used."""
+    return "XI_VEC_XVEC" if spec.pooling_func == "XI" else "XVEC"
+
+
+def xvec_min_frames(spec: ModelSpec) -> int:
+    """T' = T - 14 frames reach the pooling: XI needs one, TSTP's unbiased variance two."""
+    return XVEC_SHRINK + (1 if spec.pooling_func == "XI" else 2)
+
+
+def xvec_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of XVEC (tdnn.py:23-91): five TDNN layers whose BatchNorm has no affine
+    (running statistics only), the pooling layer's parameters (XI only), seg_1, seg_bn_1, seg_2."""
+    out: ParamList = []
+    cin = spec.feat_dim
+    for i, (k, _) in enumerate(XVEC_FRAMES, 1):
+        cout = XVEC_STATS if i == 5 else XVEC_HID
+        p = f"frame_{i}"
+        out += [(p + ".conv_1d.weight", (cout, cin, k)), (p + ".conv_1d.bias", (cout,)),
+                (p + ".bn.running_mean", (cout,)), (p + ".bn.running_var", (cout,)), (p + ".bn.num_batches_tracked", ())]
+        cin = cout
+    xi = spec.pooling_func == "XI"
+    if xi:
+        out += xi_params("pool", XVEC_STATS)
+    E = spec.embed_dim
+    out += [("seg_1.weight", (E, XVEC_STATS * (1 if xi else 2))), ("seg_1.bias", (E,)),
+            ("seg_bn_1.running_mean", (E,)), ("seg_bn_1.running_var", (E,)), ("seg_bn_1.num_batches_tracked", ()),
+            ("seg_2.weight", (E, E)), ("seg_2.bias", (E,))]
+    return out
+
+
 def ecapa_params(spec: ModelSpec) -> ParamList:
-    """state_dict layout of ECAPA_TDNN (ecapa_tdnn.py:160-206)."""
-    C, glob = ECAPA_ARCHS[spec.arch]
+    """state_dict layout of ECAPA_TDNN (ecapa_tdnn.py:160-206); the XI_VEC_ECAPA_TDNN_* names carry
+    the XI pooling layer and a 1536-wide head."""
+    xi = spec.arch in XI_ECAPA_ARCHS
+    C, glob = (XI_ECAPA_ARCHS[spec.arch], False) if xi else ECAPA_ARCHS[spec.arch]
     w = C // 8
     out: ParamList = [("layer1.conv.weight", (C, spec.feat_dim, 5)), ("layer1.conv.bias", (C,))]
     out += _bn("layer1.bn", C)
@@ -185,10 +275,14 @@ def ecapa_params(spec: ModelSpec) -> ParamList:
         out += [(f"{p}.3.linear1.weight", (128, C)), (f"{p}.3.linear1.bias", (128,)),
                 (f"{p}.3.linear2.weight", (C, 128)), (f"{p}.3.linear2.bias", (C,))]
     out += [("conv.weight", (1536, 3 * C, 1)), ("conv.bias", (1536,))]
-    out += [("pool.linear1.weight", (128, 1536 * (3 if glob else 1), 1)), ("pool.linear1.bias", (128,)),
-            ("pool.linear2.weight", (1536, 128, 1)), ("pool.linear2.bias", (1536,))]
-    out += _bn("bn", 3072)
-    out += [("linear.weight", (spec.embed_dim, 3072)), ("linear.bias", (spec.embed_dim,))]
+    if xi:
+        out += xi_params("pool", 1536)
+    else:
+        out += [("pool.linear1.weight", (128, 1536 * (3 if glob else 1), 1)), ("pool.linear1.bias", (128,)),
+                ("pool.linear2.weight", (1536, 128, 1)), ("pool.linear2.bias", (1536,))]
+    pooled = 1536 if xi else 3072
+    out += _bn("bn", pooled)
+    out += [("linear.weight", (spec.embed_dim, pooled)), ("linear.bias", (spec.embed_dim,))]
     if spec.emb_bn:
         out += _bn("bn2", spec.embed_dim)
     return out
@@ -364,6 +458,8 @@ def gemini_params(spec: ModelSpec) -> ParamList:
 
 
 def param_list(spec: ModelSpec) -> ParamList:
+    if spec.family == "xvec":
+        return xvec_params(spec)
     if spec.family == "gemini":
         return gemini_params(spec)
     if spec.family == "campplus":
@@ -375,6 +471,22 @@ def param_list(spec: ModelSpec) -> ParamList:
     if spec.family == "simam":
         return simam_params(spec)
     return resnet_params(spec)
+
+
+def xvec_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one XVEC forward over T frames: every TDNN layer at the
+    frames it keeps, XI's two 1x1 convs, seg_1 and seg_2."""
+    macs, t, cin = 0, T, spec.feat_dim
+    for i, (k, d) in enumerate(XVEC_FRAMES, 1):
+        t -= (k - 1) * d
+        cout = XVEC_STATS if i == 5 else XVEC_HID
+        macs += t * cout * cin * k
+        cin = cout
+    xi = spec.pooling_func == "XI"
+    if xi:
+        macs += t * 2 * XVEC_STATS * XI_HIDDEN
+    macs += XVEC_STATS * (1 if xi else 2) * spec.embed_dim + spec.embed_dim ** 2
+    return 2.0 * macs / 1e9
 
 
 def simam_gflop_per_utt(spec: ModelSpec, T: int) -> float:
@@ -487,8 +599,12 @@ def resnet_gflop_per_utt(spec: ModelSpec, T: int) -> float:
 
 def ecapa_gflop_per_utt(spec: ModelSpec, T: int) -> float:
     """Algorithmic FLOPs (2 x MACs) of one ECAPA forward over T frames."""
-    C, glob = ECAPA_ARCHS[spec.arch]
+    xi = spec.arch in XI_ECAPA_ARCHS
+    C, glob = (XI_ECAPA_ARCHS[spec.arch], False) if xi else ECAPA_ARCHS[spec.arch]
     w = C // 8
+    if xi:  # the trunk, XI's lin1 / lin2 (1536 <-> 256), the 1536-wide head
+        return 2.0 * (spec.feat_dim * 5 * C * T + 3 * (2 * C * C * T + 7 * w * w * 3 * T + 2 * C * 128)
+                      + 3 * C * 1536 * T + 2 * 1536 * XI_HIDDEN * T + 1536 * spec.embed_dim) / 1e9
     macs = spec.feat_dim * 5 * C * T                       # layer1
     macs += 3 * (2 * C * C * T + 7 * w * w * 3 * T + 2 * C * 128)  # blocks
     macs += 3 * C * 1536 * T                                # conv

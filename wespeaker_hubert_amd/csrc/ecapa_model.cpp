@@ -11,9 +11,13 @@
 //   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
 //           -> online-softmax attentive mean/std          -> [B][3072]
 //   head    BN(3072) + Linear (+ bn2) folded into one GEMV -> embed [B][D]
+// XI_VEC_ECAPA_TDNN_*: the same trunk; the pooling stage is XI (pooling_layers.py class XI):
+//   XI      lin1 (1536 -> 256, ReLU -> BN) -> lin2 (256 -> 1536) -> launch_xi_pool -> [B][1536]
+//   head    BN(1536) + Linear (+ bn2), the same fold with K = 1536
 #include "astp_fused.h"
 #include "model_impl.h"
 #include "res2_chain.h"
+#include "xi_pool.h"
 
 namespace wsp {
 
@@ -22,6 +26,7 @@ struct Ecapa final : Model::Impl {
   using Impl::Impl;
   int C = 512;
   bool glob = false;
+  bool xi = false;  // XI pooling instead of ASTP (the XI_VEC_ECAPA_TDNN_* names)
   ConvW layer1;
   struct Block {
     ConvW c1, c3, res2[7];
@@ -34,7 +39,9 @@ struct Ecapa final : Model::Impl {
   ConvW conv_g;                // conv with W_b + W_c in its middle third (option "cat_gate")
   void* pool2_frag = nullptr;  // pool.linear2 in MFMA B-fragment order for astp_fused.hip
   LinW pool1_ctx;
+  float *prior_mean = nullptr, *prior_logprec = nullptr;  // XI (pool1 / pool2 hold lin1 / lin2)
   LinW head;
+  int pooled_dim() const { return xi ? 1536 : 3072; }
 
   void build_params() override;
   void pack_res2(Block& b, const std::string& p, int w);
@@ -46,19 +53,29 @@ struct Ecapa final : Model::Impl {
   // kernels then (per-utterance lengths come from seg).
   void forward_chunk(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
                      const int* seg = nullptr, int M_seg = 0);
+  int min_frames() const override { return xi ? 1 : 2; }
+  bool has_segments() const override { return true; }
+  size_t ws_floats_segments(int B, int M) const override;
+  void forward_segments(const float* feats, int B, const int* seg, int M, float* embed, float* ws,
+                        hipStream_t s) override {
+    forward_chunk(feats, B, 1, embed, ws, s, seg, M);  // T unused when segmented
+  }
 };
 }  // namespace
 
 Model::Impl* make_ecapa(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
-  if (arch != "ECAPA_TDNN_c512" && arch != "ECAPA_TDNN_GLOB_c512" && arch != "ECAPA_TDNN_c1024" &&
+  const bool xi = arch == "XI_VEC_ECAPA_TDNN_c512" || arch == "XI_VEC_ECAPA_TDNN_c1024";
+  if (!xi && arch != "ECAPA_TDNN_c512" && arch != "ECAPA_TDNN_GLOB_c512" && arch != "ECAPA_TDNN_c1024" &&
       arch != "ECAPA_TDNN_GLOB_c1024")
     return nullptr;
+  WSP_CHECK(!(xi && two_emb), "XI_VEC_ECAPA_TDNN has no two_emb_layer");
   WSP_CHECK(feat_dim > 0 && feat_dim % 4 == 0, "ECAPA feat_dim must be a positive multiple of 4");
   WSP_CHECK(embed_dim > 0, "embed_dim must be positive");
   Ecapa* m = new Ecapa(arch, feat_dim, embed_dim, emb_bn, two_emb);
   m->opt.x3_variant = 7;  // 6 (the 256 x 256 tile on 16x16x32 MFMAs, r3) with LDS-DMA staging (r4)
   m->C = (arch.find("c1024") != std::string::npos) ? 1024 : 512;
   m->glob = arch.find("GLOB") != std::string::npos;
+  m->xi = xi;
   return m;
 }
 
@@ -87,12 +104,22 @@ void Ecapa::build_params() {
   }
   add("conv.weight", {1536, 3 * C, 1});
   add("conv.bias", {1536});
-  add("pool.linear1.weight", {128, glob ? 4608 : 1536, 1});
-  add("pool.linear1.bias", {128});
-  add("pool.linear2.weight", {1536, 128, 1});
-  add("pool.linear2.bias", {1536});
-  add_bn("bn", 3072);
-  add("linear.weight", {embed_dim, 3072});
+  if (xi) {
+    add("pool.prior_mean", {1, 1536});
+    add("pool.prior_logprec", {1, 1536});
+    add("pool.lin1_relu_bn.0.weight", {256, 1536, 1});
+    add("pool.lin1_relu_bn.0.bias", {256});
+    add_bn("pool.lin1_relu_bn.2", 256);
+    add("pool.lin2.weight", {1536, 256, 1});
+    add("pool.lin2.bias", {1536});
+  } else {
+    add("pool.linear1.weight", {128, glob ? 4608 : 1536, 1});
+    add("pool.linear1.bias", {128});
+    add("pool.linear2.weight", {1536, 128, 1});
+    add("pool.linear2.bias", {1536});
+  }
+  add_bn("bn", pooled_dim());
+  add("linear.weight", {embed_dim, pooled_dim()});
   add("linear.bias", {embed_dim});
   if (emb_bn) add_bn("bn2", embed_dim);
 }
@@ -146,9 +173,15 @@ void Ecapa::finalize() {
       }
     conv_g = pack_conv(wg, 1536, 3 * C, 1, P("conv.bias").data(), "");
   }
-  const auto& l1 = P("pool.linear1.weight");
-  const int l1k = glob ? 4608 : 1536;
-  {
+  if (xi) {
+    pool1 = pack_conv(P("pool.lin1_relu_bn.0.weight"), 256, 1536, 1, P("pool.lin1_relu_bn.0.bias").data(),
+                      "pool.lin1_relu_bn.2");
+    pool2 = pack_conv(P("pool.lin2.weight"), 1536, 256, 1, P("pool.lin2.bias").data(), "");
+    prior_mean = dev.upload(P("pool.prior_mean"));
+    prior_logprec = dev.upload(P("pool.prior_logprec"));
+  } else {
+    const auto& l1 = P("pool.linear1.weight");
+    const int l1k = glob ? 4608 : 1536;
     std::vector<float> wx((size_t)128 * 1536);
     for (int n = 0; n < 128; ++n)
       for (int k = 0; k < 1536; ++k) wx[(size_t)n * 1536 + k] = l1[(size_t)n * l1k + k];
@@ -158,9 +191,9 @@ void Ecapa::finalize() {
       // folded into a per-utterance bias computed by small_linear.
       pool1_ctx = pack_lin(l1.data() + 1536, 128, 3072, l1k, P("pool.linear1.bias").data());
     }
+    pool2 = pack_conv(P("pool.linear2.weight"), 1536, 128, 1, P("pool.linear2.bias").data(), "");
+    pool2_frag = pack_frag(P("pool.linear2.weight"), 1536, 128);
   }
-  pool2 = pack_conv(P("pool.linear2.weight"), 1536, 128, 1, P("pool.linear2.bias").data(), "");
-  pool2_frag = pack_frag(P("pool.linear2.weight"), 1536, 128);
   // head: y = Linear(BN(p)) [-> bn2] folded to y = W' p + b'
   {
     std::vector<double> s, t;
@@ -170,17 +203,18 @@ void Ecapa::finalize() {
     const int D = embed_dim;
     std::vector<double> s2(D, 1.0), t2(D, 0.0);
     if (emb_bn) bn_affine("bn2", s2, t2);
-    std::vector<float> wf((size_t)D * 3072), bf(D);
+    const int K = pooled_dim();
+    std::vector<float> wf((size_t)D * K), bf(D);
     for (int n = 0; n < D; ++n) {
       double acc = bb[n];
-      for (int k = 0; k < 3072; ++k) {
-        const double wv = W[(size_t)n * 3072 + k];
-        wf[(size_t)n * 3072 + k] = (float)(s2[n] * wv * s[k]);
+      for (int k = 0; k < K; ++k) {
+        const double wv = W[(size_t)n * K + k];
+        wf[(size_t)n * K + k] = (float)(s2[n] * wv * s[k]);
         acc += wv * t[k];
       }
       bf[n] = (float)(s2[n] * acc + t2[n]);
     }
-    head = pack_lin(wf.data(), D, 3072, 3072, bf.data());
+    head = pack_lin(wf.data(), D, K, K, bf.data());
   }
 }
 
@@ -198,7 +232,8 @@ struct EcapaWs {
   double* sesum;  // SE column-sum partials (f64)
   size_t floats;
 };
-EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base) {
+// xi: the attention hidden layer is 256 wide (XI's lin1) instead of 128
+EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base, bool xi) {
   WsCursor c{base};
   EcapaWs w;
   w.x[0] = nullptr;
@@ -210,7 +245,7 @@ EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base) {
   w.ghid = c.take(B * 128);
   w.gate = c.take(B * C);
   w.xp = c.take(M * 1536);
-  w.att = c.take(M * 128);
+  w.att = c.take(M * (xi ? 256 : 128));
   w.logit = c.take(M * 1536);
   w.gstats = c.take(B * 3072);
   w.rowb = c.take(B * 128);
@@ -223,8 +258,10 @@ EcapaWs ecapa_ws(size_t C, size_t B, size_t M, float* base) {
 
 size_t Ecapa::ws_floats(int B, int T) const {
   const size_t bc = chunk(B, T);
-  return ecapa_ws(C, bc, bc * T, nullptr).floats;
+  return ecapa_ws(C, bc, bc * T, nullptr, xi).floats;
 }
+
+size_t Ecapa::ws_floats_segments(int B, int M) const { return ecapa_ws(C, B, M, nullptr, xi).floats; }
 
 void Ecapa::forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) {
   const int bc = chunk(B, T);
@@ -235,7 +272,7 @@ void Ecapa::forward(const float* feats, int B, int T, float* embed, float* ws, h
 void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s,
                           const int* seg, int M_seg) {
   const int M = seg ? M_seg : B * T, w = C / 8;
-  const EcapaWs W = ecapa_ws(C, B, M, ws);
+  const EcapaWs W = ecapa_ws(C, B, M, ws, xi);
   float* const* x = W.x;
   float *h1 = W.h1, *h2 = W.h2, *h3 = W.h3, *xp = W.xp;
   // SE squeeze fused into conv3's epilogue (per-utterance f64 column sums) on the
@@ -343,6 +380,17 @@ void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float*
       launch_small_linear({W.gstats, 3072, pool1_ctx.wt, pool1_ctx.bias, W.rowb, 128, B, 3072, 128, 0}, s);
     });
   }
+  if (xi) {
+    // XI: logits z = lin2(BN(ReLU(lin1 xp))), then the Gaussian posterior mean over frames + prior
+    gemm("xi_lin1", pool1, xp, 1536, W.att, 256, M, T, 1, 0, kActRelu, s, seg, B);
+    gemm("xi_lin2", pool2, W.att, 256, W.logit, 1536, M, T, 1, 0, kActNone, s, seg, B);
+    const XiPoolArgs a{W.logit, 1536, xp, 1536, prior_mean, prior_logprec, B, T, 1536, seg, W.pooled, 1536};
+    run("xi_pool", 0, s, [&] { launch_xi_pool(a, s); });
+    run("head", 0, s, [&] {
+      launch_small_linear({W.pooled, 1536, head.wt, head.bias, embed, embed_dim, B, 1536, embed_dim, 0}, s);
+    });
+    return;
+  }
   // GLOB: the context's per-utterance row bias carries pool.linear1's bias
   gemm("pool_linear1", pool1, xp, 1536, W.att, 128, M, T, 1, 0, kActTanh, s, seg, B, glob ? W.rowb : nullptr, !glob);
   if (opt.precision == 1 && opt.astp_fused) {
@@ -356,30 +404,6 @@ void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float*
   run("head", 0, s, [&] {
     launch_small_linear({W.pooled, 3072, head.wt, head.bias, embed, embed_dim, B, 3072, embed_dim, 0}, s);
   });
-}
-
-// ------------------------------------------------------------ Model API ---
-static Ecapa& as_ecapa(Model::Impl* m) {
-  Ecapa* e = dynamic_cast<Ecapa*>(m);
-  WSP_CHECK(e, "segmented batches are implemented for ECAPA-TDNN handles");
-  return *e;
-}
-
-size_t Model::workspace_bytes_segments(int B, int M) const {
-  const Ecapa& m = as_ecapa(impl);
-  WSP_CHECK(B > 0 && M >= B, "segmented batch needs B >= 1 and M >= B rows");
-  return ecapa_ws(m.C, B, M, nullptr).floats * sizeof(float) + 256;
-}
-
-void Model::forward_segments(const float* feats, int B, const int* seg, int M, float* embed, void* ws,
-                             size_t ws_bytes, hipStream_t s) {
-  Ecapa& m = as_ecapa(impl);
-  WSP_CHECK(m.finalized, "forward before finalize");
-  WSP_CHECK(seg != nullptr && B > 0 && M >= B, "segmented batch needs offsets, B >= 1 and M >= B rows");
-  WSP_CHECK((size_t)M * 1536 < (1u << 31) / 4, "segmented batch too large");
-  WSP_CHECK(ws_bytes >= workspace_bytes_segments(B, M), "workspace too small");
-  float* wsf = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
-  m.forward_chunk(feats, B, 1, embed, wsf, s, seg, M);  // T unused when segmented
 }
 
 }  // namespace wsp

@@ -3,7 +3,7 @@
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
 // The families derive from Model::Impl: their tables, folds, workspace layouts and forward
 // schedules are in ecapa_model.cpp, resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp,
-// campplus_model.cpp, eres2net_model.cpp and gemini_model.cpp; Model::create below is the one place here that names them.
+// campplus_model.cpp, eres2net_model.cpp, gemini_model.cpp and xvec_model.cpp; Model::create below is the one place here that names them.
 #include "model_impl.h"
 
 namespace wsp {
@@ -175,7 +175,7 @@ Model::~Model() { delete impl; }
 
 void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
   WSP_CHECK(!impl, "model already created");
-  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini})
+  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec})
     if ((impl = make(arch, feat_dim, embed_dim, emb_bn, two_emb))) break;
   WSP_CHECK(impl, "unsupported arch " + arch);
   // Creation and parameter intake are host-only; the device is bound at
@@ -237,7 +237,10 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
   Impl& m = *impl;
   WSP_CHECK(!m.is_frontend(), "HuBERT handle: use the front-end forward");
   WSP_CHECK(m.finalized, "forward before finalize");
-  WSP_CHECK(B > 0 && T > 1, "forward needs B >= 1 and T >= 2 frames");
+  if (m.min_frames() >= 2)
+    WSP_CHECK(B > 0 && T > 1, "forward needs B >= 1 and T >= 2 frames");
+  else  // XI pooling is defined on one frame (the prior is its second entry)
+    WSP_CHECK(B > 0 && T >= 1, "forward needs B >= 1 and T >= 1 frames");
   WSP_CHECK((size_t)B * T < (1u << 31), "B*T too large");
   WSP_CHECK(ws_bytes >= workspace_bytes(B, T), "workspace too small");
   m.check_forward(B, T);
@@ -252,6 +255,25 @@ void Model::forward(const float* feats, int B, int T, float* embed, void* ws, si
     wsb += m.ws_bytes_one(nb, T);
   }
   if (ns > 1) m.join(s, ns);
+}
+
+// Ragged batches: one launch sequence over all M rows (no chunking, no sub-batch streams).
+size_t Model::workspace_bytes_segments(int B, int M) const {
+  WSP_CHECK(impl->has_segments(), "segmented batches are implemented for ECAPA-TDNN handles");
+  WSP_CHECK(B > 0 && M >= B, "segmented batch needs B >= 1 and M >= B rows");
+  return impl->ws_floats_segments(B, M) * sizeof(float) + 256;
+}
+
+void Model::forward_segments(const float* feats, int B, const int* seg, int M, float* embed, void* ws,
+                             size_t ws_bytes, hipStream_t s) {
+  Impl& m = *impl;
+  WSP_CHECK(m.has_segments(), "segmented batches are implemented for ECAPA-TDNN handles");
+  WSP_CHECK(m.finalized, "forward before finalize");
+  WSP_CHECK(seg != nullptr && B > 0 && M >= B, "segmented batch needs offsets, B >= 1 and M >= B rows");
+  WSP_CHECK((size_t)M * 1536 < (1u << 31) / 4, "segmented batch too large");
+  WSP_CHECK(ws_bytes >= workspace_bytes_segments(B, M), "workspace too small");
+  float* wsf = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+  m.forward_segments(feats, B, seg, M, embed, wsf, s);
 }
 
 void Model::profile(bool on) {

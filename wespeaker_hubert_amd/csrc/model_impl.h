@@ -5,6 +5,7 @@
 //   ecapa_model.cpp   Ecapa     resnet_model.cpp    ResNet (and SimAM-ResNet)
 //   hubert_model.cpp  Hubert    campplus_model.cpp  Campplus
 //   eres2net_model.cpp  Eres2Net  gemini_model.cpp  Gemini
+//   xvec_model.cpp    Xvec (XVEC with TSTP, XI_VEC_XVEC with XI pooling)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -187,9 +188,15 @@ struct Model::Impl {
   // a front-end handle takes the wsp_frontend_* calls instead of forward / workspace_bytes
   virtual bool is_frontend() const { return false; }
   virtual void check_forward(int B, int T) const {}  // the family's forward preconditions
+  virtual int min_frames() const { return 2; }  // the shortest uniform batch forward() takes at all
   // one sub-batch of B utterances of T frames (the family applies its own chunk rule inside)
   virtual size_t ws_floats(int B, int T) const = 0;
   virtual void forward(const float* feats, int B, int T, float* embed, float* ws, hipStream_t s) = 0;
+  // ragged batches (ECAPA-TDNN, x-vector): utterance b = rows [seg[b], seg[b+1]) of M rows in all
+  virtual bool has_segments() const { return false; }
+  virtual size_t ws_floats_segments(int B, int M) const { return 0; }
+  virtual void forward_segments(const float* feats, int B, const int* seg, int M, float* embed, float* ws,
+                                hipStream_t s) {}
 
   // sub-batch streams (option "streams")
   std::vector<hipStream_t> sub_st;  // streams 1.. (range 0 runs on the caller's stream)
@@ -257,6 +264,6 @@ struct Model::Impl {
 // One per family, defined beside its subclass: the arch names the family serves, their argument
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
-MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini;
+MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec;
 
 }  // namespace wsp

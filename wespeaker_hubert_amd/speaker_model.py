@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arch import ModelSpec, check_arch, make_spec, param_list
+from .arch import ModelSpec, check_arch, make_spec, param_list, xvec_handle_arch, xvec_min_frames
 
 logger = logging.getLogger(__name__)
 
@@ -184,7 +184,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Gemini DF-ResNet speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Gemini DF-ResNet / x-vector speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -196,7 +196,8 @@ class HipSpeakerModel(_HipHandle):
 
     def _create_args(self):
         s = self.spec
-        return s.arch, s.feat_dim, s.embed_dim, s.emb_bn, s.two_emb_layer
+        arch = xvec_handle_arch(s) if s.family == "xvec" else s.arch  # (XVEC, pooling_func='XI') = XI_VEC_XVEC
+        return arch, s.feat_dim, s.embed_dim, s.emb_bn, s.two_emb_layer
 
     # ----------------------------------------------------------- forward --
     def workspace_bytes(self, B: int, T: int) -> int:
@@ -229,7 +230,7 @@ class HipSpeakerModel(_HipHandle):
 
     def embed_segments(self, feats: torch.Tensor, frame_offsets: torch.Tensor,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Ragged batch (ECAPA-TDNN): utterance b = rows [off[b], off[b+1]) of feats
+        """Ragged batch (ECAPA-TDNN, x-vector): utterance b = rows [off[b], off[b+1]) of feats
         [sum T_b][feat_dim]; frame_offsets = int32 [B+1] on the same device.  Each row of
         the result equals embed(feats_b[None])."""
         if not feats.is_cuda or not frame_offsets.is_cuda:
@@ -241,6 +242,11 @@ class HipSpeakerModel(_HipHandle):
         feats = feats.float().contiguous()
         off = frame_offsets.to(torch.int32).contiguous()
         B, M = off.numel() - 1, feats.shape[0]
+        if self.spec.family == "xvec":
+            # the unpadded convs keep T_b - 14 frames: a shorter utterance has nothing to pool
+            need = xvec_min_frames(self.spec)
+            if B > 0 and int((off[1:] - off[:-1]).min()) < need:
+                raise RuntimeError(f"{xvec_handle_arch(self.spec)} needs >= {need} frames per utterance")
         if out is None:
             out = torch.empty(B, self.spec.embed_dim, dtype=torch.float32, device=feats.device)
         b = ctypes.c_size_t()
@@ -255,13 +261,14 @@ class HipSpeakerModel(_HipHandle):
 
     @property
     def supports_segments(self) -> bool:
-        return self.spec.family == "ecapa"
+        return self.spec.family in ("ecapa", "xvec")
 
     def __call__(self, feats: torch.Tensor):
         # SimAM_ResNet*_ASP.forward and CAMPPlus.forward return the embedding itself
         # (samresnet.py:135-143, campplus.py:409-413); ECAPA / ResNet return (aux, embed)
         # as does ERes2Net.forward (eres2net.py:380-391); Gemini_DF_ResNet.forward returns
-        # (tensor(0.), embed) like ResNet (gemini_dfresnet.py:129-141)
+        # (tensor(0.), embed) like ResNet (gemini_dfresnet.py:129-141); XVEC.forward returns
+        # (embed_a, embed_b) and outputs[-1] = embed_b is the embedding (tdnn.py:109-118)
         if self.spec.family in ("simam", "campplus", "eres2net"):
             return self.embed(feats)
         return None, self.embed(feats)

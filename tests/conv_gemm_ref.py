@@ -18,18 +18,20 @@ tanh and GELU are checked in two steps instead (`act_expected`): the same operan
 are held to the bound above, then the kernel's activation output is compared with the float64
 activation of the kernel's OWN act-none output, within the activation's own error.
 
-Case files: see the head comment of tools/conv_gemm_run.cpp.  `write_cases` / `read_cases` /
-`read_results` are the Python side of that format.
+Case files: `op_cases` / `read_cases` / `results_of` map a case onto the header, arrays, results and
+own words of tools/conv_gemm_run.cpp's op table; the file format itself is tests/op_runner.py's.
 """
 import math
-import struct
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-MAGIC_IN, MAGIC_OUT, VERSION, OP_CONV_GEMM = 0x43505357, 0x52505357, 1, 1
-FILL = 0x7FC5A5A5
+import op_runner
+from op_runner import FILL  # noqa: F401
+
+MAGIC, OP_CONV_GEMM = 0x43505357, 1
+NH = op_runner.LAYOUT["conv_gemm_run"][0]  # 42 ints + ln_eps
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU = 0, 1, 2, 3
 EPS24 = 2.0 ** -24
 
@@ -94,108 +96,68 @@ def _header(c):
     return [int(h[k]) for k in HDR]
 
 
-def _arr(buf, x, dtype):
-    x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
-    buf.append(struct.pack("<I", x.size))
-    buf.append(x.astype("<" + np.dtype(dtype).str[1:]).tobytes())
+# optional arrays in file order: (flag bit, keys); the a[] buffers and `colsum` have no key of their own
+_OPTIONAL = ((F_BIAS, ("bias",)), (F_ROWBIAS, ("row_bias",)), (F_RES, ("res",)), (F_SCALE, ("scale", "shift")),
+             (F_SEG, ("seg",)), (F_ISEG, ("iseg",)), (F_LNIN, ("ln_in",)), (F_LNCS, ("ln_cs",)), (F_LNGB, ("ln_g", "ln_b")))
+_INT_KEYS = ("seg", "iseg")
 
 
-def write_cases(path, cases):
-    buf = [struct.pack("<III", MAGIC_IN, VERSION, len(cases))]
-    for c in cases:
-        buf.append(struct.pack("<I", OP_CONV_GEMM))
-        buf.append(struct.pack(f"<{len(HDR)}i", *_header(c)))
-        buf.append(struct.pack("<f", c["ln_eps"]))
-        for x in c["a"]:
-            if x is not None:
-                _arr(buf, x, np.float32)
-        _arr(buf, c["w"], np.float32)
-        for key in ("bias", "row_bias", "res"):
-            if c[key] is not None:
-                _arr(buf, c[key], np.float32)
-        if c["scale"] is not None:
-            _arr(buf, c["scale"], np.float32)
-            _arr(buf, c["shift"], np.float32)
-        for key in ("seg", "iseg"):
-            if c[key] is not None:
-                _arr(buf, c[key], np.int32)
-        for key in ("ln_in", "ln_cs"):
-            if c[key] is not None:
-                _arr(buf, c[key], np.float32)
-        if c["ln_g"] is not None:
-            _arr(buf, c["ln_g"], np.float32)
-            _arr(buf, c["ln_b"], np.float32)
-    with open(path, "wb") as f:
-        f.write(b"".join(buf))
-
-
-class _Cursor:
-    def __init__(self, data):
-        self.d, self.o = data, 0
-
-    def take(self, fmt):
-        v = struct.unpack_from("<" + fmt, self.d, self.o)
-        self.o += struct.calcsize("<" + fmt)
-        return v
-
-    def arr(self, dtype):
-        (n,) = self.take("I")
-        x = np.frombuffer(self.d, dtype=np.dtype(dtype).newbyteorder("<"), count=n, offset=self.o).copy()
-        self.o += n * np.dtype(dtype).itemsize
-        return x
-
-
-def read_cases(path):
-    """The reader of the case format (the Python twin of the runner's parser)."""
-    with open(path, "rb") as f:
-        cur = _Cursor(f.read())
-    magic, version, n = cur.take("III")
-    assert magic == MAGIC_IN and version == VERSION
-    out = []
-    for _ in range(n):
-        (op,) = cur.take("I")
-        assert op == OP_CONV_GEMM
-        h = dict(zip(HDR, cur.take(f"{len(HDR)}i")))
-        (h["ln_eps"],) = cur.take("f")
-        fl = h["flags"]
-        h["a"] = [cur.arr(np.float32).reshape(h[f"arows{i}"], h[f"lda{i}"]) if fl & (1 << i) else None
-                  for i in range(3)]
-        h["w"] = cur.arr(np.float32).reshape(h["N"], h["cin"], h["taps"])
-        h["bias"] = cur.arr(np.float32) if fl & F_BIAS else None
-        h["row_bias"] = cur.arr(np.float32).reshape(h["B"], h["N"]) if fl & F_ROWBIAS else None
-        h["res"] = cur.arr(np.float32).reshape(h["M"], h["ldres"]) if fl & F_RES else None
-        h["scale"] = cur.arr(np.float32) if fl & F_SCALE else None
-        h["shift"] = cur.arr(np.float32) if fl & F_SCALE else None
-        h["seg"] = cur.arr(np.int32) if fl & F_SEG else None
-        h["iseg"] = cur.arr(np.int32) if fl & F_ISEG else None
-        h["colsum"] = bool(fl & F_COLSUM)
-        h["ln_in"] = cur.arr(np.float32) if fl & F_LNIN else None
-        h["ln_cs"] = cur.arr(np.float32) if fl & F_LNCS else None
-        h["ln_g"] = cur.arr(np.float32) if fl & F_LNGB else None
-        h["ln_b"] = cur.arr(np.float32) if fl & F_LNGB else None
-        out.append(h)
-    assert cur.o == len(cur.d), "trailing bytes"
+def _arrays(c):
+    """The case's arrays in the op table's order: a[0..2], w, then the flagged ones."""
+    out = [np.asarray(x, np.float32) for x in c["a"] + [c["w"]] if x is not None]
+    for bit, keys in _OPTIONAL:
+        if _flags(c) & bit:
+            out += [np.asarray(c[k], np.int32 if k in _INT_KEYS else np.float32) for k in keys]
     return out
 
 
-def read_results(path, cases):
-    with open(path, "rb") as f:
-        cur = _Cursor(f.read())
-    magic, n = cur.take("II")
-    assert magic == MAGIC_OUT and n == len(cases)
+def op_cases(cases):
+    """(op, header, arrays) per case; ln_eps travels as f32 in the header's last word."""
+    return [(OP_CONV_GEMM, _header(c) + [int(np.float32(c["ln_eps"]).view(np.int32))], _arrays(c)) for c in cases]
+
+
+def write_cases(path, cases):
+    op_runner.write_cases(path, MAGIC, op_cases(cases), NH)
+
+
+def _narrays(op, hdr):
+    assert op == OP_CONV_GEMM
+    fl = hdr[HDR.index("flags")]
+    return bin(fl & 7).count("1") + 1 + sum(len(keys) for bit, keys in _OPTIONAL if fl & bit)
+
+
+def read_cases(path):
+    """Header fields by name and arrays by key, shaped as the header says (the reverse of write_cases)."""
+    out = []
+    for _, hdr, arrays in op_runner.read_cases(path, MAGIC, NH, _narrays):
+        h = dict(zip(HDR, hdr))
+        h["ln_eps"] = float(np.int32(hdr[-1]).view(np.float32))
+        arrays = iter(arrays)
+        fl = h["flags"]
+        h["a"] = [next(arrays).reshape(h[f"arows{i}"], h[f"lda{i}"]) if fl & (1 << i) else None for i in range(3)]
+        h["w"] = next(arrays).reshape(h["N"], h["cin"], h["taps"])
+        for bit, keys in _OPTIONAL:
+            for k in keys:
+                h[k] = (next(arrays).view(np.int32) if k in _INT_KEYS else next(arrays)) if fl & bit else None
+        if h["row_bias"] is not None:
+            h["row_bias"] = h["row_bias"].reshape(h["B"], h["N"])
+        if h["res"] is not None:
+            h["res"] = h["res"].reshape(h["M"], h["ldres"])
+        h["colsum"] = bool(fl & F_COLSUM)
+        out.append(h)
+    return out
+
+
+def results_of(raw, cases):
+    """op_runner results -> status, message, tile and block_rows (the record's own words), out, means, ln_out."""
     res = []
-    for c in cases:
-        (status,) = cur.take("I")
-        (tile,) = cur.take("24s")
-        (bm,) = cur.take("i")
-        msg = cur.arr(np.uint8).tobytes().decode()
-        r = dict(status=status, tile=tile.split(b"\0")[0].decode(), block_rows=bm, message=msg)
-        if status == 0:
-            r["out"] = cur.arr(np.float32).reshape(c["M"] + 8, c["ldo"])
-            r["means"] = cur.arr(np.float32)
-            r["ln_out"] = cur.arr(np.float32)
+    for c, r in zip(cases, raw):
+        tile, bm = r["own"][:24].split(b"\0")[0].decode(), int.from_bytes(r["own"][24:], "little", signed=True)
+        r = dict(status=r["status"], message=r["message"], tile=tile, block_rows=bm, arrays=r["arrays"])
+        if r["status"] == 0:
+            out, r["means"], r["ln_out"] = r.pop("arrays")
+            r["out"] = out.reshape(c["M"] + 8, c["ldo"])
         res.append(r)
-    assert cur.o == len(cur.d), "trailing bytes"
     return res
 
 

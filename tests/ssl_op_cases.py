@@ -1,6 +1,6 @@
 """Cases of the SSL front end's op-level conformance tests (tests/test_gpu_ssl_op.py on the MI355X,
-tests/test_ssl_op_ref_cpu.py against the numpy emulations), and the Python side of tools/ssl_run's
-file format (its head comment).
+tests/test_ssl_op_ref_cpu.py against the numpy emulations), and their header ints and arrays as the op
+table of tools/ssl_run.cpp lists them (`_hdr_arrays`; the file format is tests/op_runner.py's, with 16 header ints).
 
 Attention: H = 2 unless stated, dh = 64, ldq = 3 H 64 + 8 and ldo = H 64 + 4, so strides differ
 from widths; the pad columns of qkv are random.  Uniform batches travel without `seg`, ragged ones
@@ -18,13 +18,11 @@ units, f = the key's 32-key chunk (or an indicator of the last key); v carries a
   last   flat at -40 with the single maximum (+20) in the last live key of the partial chunk
   brise  `rise` with flat q k and the bias supplying it: table linear in j - i, gate 2 / 0.5
 """
-import struct
-
 import numpy as np
 
 from ssl_op_ref import DH, REL_N, REL_STRIDE, rand_a, rand_w
 
-MAGIC_IN, MAGIC_OUT, VERSION = 0x53505357, 0x52505357, 1
+MAGIC = 0x53505357
 OP_ATTN, OP_GATE, OP_POS, OP_LN, OP_CONV0 = 1, 2, 3, 4, 5
 LN2 = float(np.log(2.0))
 SELECTOR_T = 257
@@ -318,7 +316,7 @@ def refused_cases():
             (c0, "bad frame count")]
 
 
-# ----------------------------------------------------------------------- file format --
+# ------------------------------------------------------------- header ints and arrays --
 def _hdr_arrays(c):
     op = c["op"]
     if op == OP_ATTN:
@@ -346,38 +344,6 @@ def _hdr_arrays(c):
     return hdr, arrs
 
 
-def write_cases(path, cases):
-    buf = [struct.pack("<III", MAGIC_IN, VERSION, len(cases))]
-    for c in cases:
-        hdr, arrs = _hdr_arrays(c)
-        buf.append(struct.pack("<I16i", c["op"], *(hdr + [0] * (16 - len(hdr)))))
-        for a in arrs:
-            a = np.ascontiguousarray(a)
-            a = a.astype("<i4") if a.dtype.kind == "i" else a.astype("<f4")
-            buf.append(struct.pack("<I", a.size))
-            buf.append(a.tobytes())
-    with open(path, "wb") as f:
-        f.write(b"".join(buf))
-
-
-def read_results(path, n):
-    buf = open(path, "rb").read()
-    magic, cnt = struct.unpack_from("<II", buf, 0)
-    assert magic == MAGIC_OUT and cnt == n
-    pos, out = 8, []
-    for _ in range(n):
-        status, ln = struct.unpack_from("<II", buf, pos)
-        pos += 8
-        msg = buf[pos:pos + ln].decode()
-        pos += ln
-        arrs = []
-        if status == 0:
-            (na,) = struct.unpack_from("<I", buf, pos)
-            pos += 4
-            for _ in range(na):
-                (m,) = struct.unpack_from("<I", buf, pos)
-                arrs.append(np.frombuffer(buf, dtype="<f4", count=m, offset=pos + 4).copy())
-                pos += 4 + 4 * m
-        out.append(dict(status=status, message=msg, arrays=arrs))
-    assert pos == len(buf), "trailing bytes"
-    return out
+def op_case(c):
+    """The case as tests/op_runner.py writes it: (op, header ints, arrays)."""
+    return (c["op"], *_hdr_arrays(c))

@@ -21,8 +21,6 @@ Measured (MI355X, these seeds): max |device - float64| 1.275e-7 over the four ma
 max |err| / bound: cam_gemm .160 (segment sums .101), cam_local .061, fcm_conv .472.
 """
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -33,13 +31,13 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import conv_gemm_ref as ref  # noqa: E402
-from conv_gemm_ref import EPS24, FILL  # noqa: E402
+import op_runner  # noqa: E402
+from conv_gemm_ref import EPS24  # noqa: E402
+from op_runner import untouched as _untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RUNNER = os.path.join(ROOT, "tools", "cam_dense_run")
-MAGIC_IN, MAGIC_OUT, SEG = 0x44505357, 0x52505357, 100
+MAGIC, SEG = 0x44505357, 100
 MEASURED_MASK_EXCESS = 0.0
 DEVICE_ERR = 4.0 * MEASURED_MASK_EXCESS
 assert DEVICE_ERR < 1e-6
@@ -124,51 +122,13 @@ CASES = [
     fcm_case(31, 2, 8, 5, 1, 0, 1), fcm_case(32, 2, 8, 5, 1, 0, 0), fcm_case(33, 3, 2, 7, 1, 1, 0),
     fcm_case(34, 3, 8, 50, 1, 0, 1), fcm_case(35, 1, 6, 101, 0, 1, 0),
 ]
-_RESULTS = {}
-
-
-def results(tmp_path_factory):
-    """One runner process for all cases."""
-    if "r" in _RESULTS:
-        return _RESULTS["r"]
-    if not os.path.exists(RUNNER):
-        pytest.fail(f"{RUNNER} not built (run __graft_entry__.build())")
-    d = tmp_path_factory.mktemp("cam_dense")
-    fin, fout = str(d / "cases.bin"), str(d / "results.bin")
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<III", MAGIC_IN, 1, len(CASES)))
-        for c in CASES:
-            f.write(struct.pack("<I8i", c["op"], *(c["hdr"] + [0] * (8 - len(c["hdr"])))))
-            for a in c["arrays"]:
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                f.write(struct.pack("<I", a.size))
-                f.write(a.tobytes())
-    p = subprocess.run([RUNNER, fin, fout], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, f"runner status {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
-    buf = open(fout, "rb").read()
-    magic, n = struct.unpack_from("<II", buf, 0)
-    assert magic == MAGIC_OUT and n == len(CASES)
-    pos, out = 8, []
-    for _ in CASES:
-        status, ln = struct.unpack_from("<II", buf, pos)
-        pos += 8
-        msg = buf[pos:pos + ln].decode()
-        pos += ln
-        arrs = []
-        if status == 0:
-            for _ in range(2):
-                (cnt,) = struct.unpack_from("<I", buf, pos)
-                arrs.append(np.frombuffer(buf, dtype=np.float32, count=cnt, offset=pos + 4).copy())
-                pos += 4 + 4 * cnt
-        out.append(dict(status=status, message=msg, arrays=arrs))
-    assert pos == len(buf)
-    _RESULTS["r"] = out
-    return out
 
 
 @pytest.fixture(scope="module")
 def res(tmp_path_factory):
-    return results(tmp_path_factory)
+    """One runner process for all cases."""
+    return op_runner.run("cam_dense_run", MAGIC, [(c["op"], c["hdr"], c["arrays"]) for c in CASES],
+                         tmp_path_factory.mktemp("cam_dense"))
 
 
 def _of(res, op):
@@ -176,10 +136,6 @@ def _of(res, op):
         if c["op"] == op:
             assert r["status"] == 0, f"case {c['hdr']} refused: {r['message']}"
             yield c, r
-
-
-def _untouched(x):
-    return (np.ascontiguousarray(x).view(np.uint32) == FILL).all()
 
 
 def _t(x):

@@ -45,7 +45,6 @@ implements no activation and GELU only: ReLU / tanh used to be dropped silently 
 refused by the library, which the test asserts, as it does for the f32 kernel given a fold.
 """
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -56,12 +55,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import conv_gemm_cases as cases  # noqa: E402
 import conv_gemm_ref as ref  # noqa: E402
+import op_runner  # noqa: E402
 from conv_gemm_ref import ACT_GELU, ACT_NONE, ACT_TANH  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RUNNER = os.path.join(ROOT, "tools", "conv_gemm_run")
 
 # Largest |device activation - float64 activation of the same f32 input| in excess of the
 # documented parts (A&S + 4 ulps), measured over groups 6, 8, 12 and 13 on an MI355X, and the
@@ -72,13 +69,7 @@ assert all(v < 1e-6 for v in DEVICE_ERR.values())
 
 
 def _run(tmp_path, launches, timeout=60):
-    if not os.path.exists(RUNNER):
-        pytest.fail(f"{RUNNER} not built (run __graft_entry__.build())")
-    fin, fout = str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")
-    ref.write_cases(fin, launches)
-    p = subprocess.run([RUNNER, fin, fout], capture_output=True, text=True, timeout=timeout)
-    assert p.returncode == 0, f"runner status {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
-    return ref.read_results(fout, launches)
+    return ref.results_of(op_runner.run("conv_gemm_run", ref.MAGIC, ref.op_cases(launches), tmp_path, timeout), launches)
 
 
 class _Group:

@@ -28,8 +28,6 @@ Measured on an MI355X (these seeds), max |err| / allowance:
 gemini_dw .227, gemini_tail .115, gemini_down .064, 1x1 convs .331.
 """
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -40,13 +38,13 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import conv_gemm_ref as ref  # noqa: E402
-from conv_gemm_ref import ACT_NONE, ACT_RELU, EPS24, FILL  # noqa: E402
+import op_runner  # noqa: E402
+from conv_gemm_ref import ACT_NONE, ACT_RELU, EPS24  # noqa: E402
+from op_runner import untouched as _untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RUNNER = os.path.join(ROOT, "tools", "gemini_run")
-MAGIC_IN, MAGIC_OUT = 0x47505357, 0x52505357
+MAGIC = 0x47505357
 DW, TAIL, DOWN, PW = 1, 2, 3, 4
 
 
@@ -134,46 +132,14 @@ CASES.append(pw_case(300, 165, 32, 128))
 CASES.append(pw_case(301, 37, 128, 512, lda=136, aoff=8, ldo=516, ooff=4))
 CASES.append(pw_case(302, 165, 128, 32, res=True))
 CASES.append(pw_case(303, 10, 1024, 256, res=True))
-_RESULTS = {}
 
 
 @pytest.fixture(scope="module")
 def res(tmp_path_factory):
     """One runner process for all cases."""
-    if "r" in _RESULTS:
-        return _RESULTS["r"]
-    if not os.path.exists(RUNNER):
-        pytest.fail(f"{RUNNER} not built (run __graft_entry__.build())")
-    d = tmp_path_factory.mktemp("gemini_op")
-    fin, fout = str(d / "cases.bin"), str(d / "results.bin")
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<III", MAGIC_IN, 1, len(CASES)))
-        for c in CASES:
-            f.write(struct.pack("<I16i", c["op"], *(c["hdr"] + [0] * (16 - len(c["hdr"])))))
-            for a in c["arrays"]:
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                f.write(struct.pack("<I", a.size))
-                f.write(a.tobytes())
-    p = subprocess.run([RUNNER, fin, fout], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, f"runner status {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
-    buf = open(fout, "rb").read()
-    magic, n = struct.unpack_from("<II", buf, 0)
-    assert magic == MAGIC_OUT and n == len(CASES)
-    pos, out = 8, []
-    for _ in CASES:
-        status, ln = struct.unpack_from("<II", buf, pos)
-        pos += 8
-        msg = buf[pos:pos + ln].decode()
-        pos += ln
-        arr = None
-        if status == 0:
-            (cnt,) = struct.unpack_from("<I", buf, pos)
-            arr = np.frombuffer(buf, dtype=np.float32, count=cnt, offset=pos + 4).copy()
-            pos += 4 + 4 * cnt
-        out.append(dict(status=status, message=msg, out=arr))
-    assert pos == len(buf)
-    _RESULTS["r"] = out
-    return out
+    out = op_runner.run("gemini_run", MAGIC, [(c["op"], c["hdr"], c["arrays"]) for c in CASES],
+                        tmp_path_factory.mktemp("gemini_op"))
+    return [dict(r, out=r["arrays"][0] if r["status"] == 0 else None) for r in out]
 
 
 def _of(res, op):
@@ -181,10 +147,6 @@ def _of(res, op):
         if c["op"] == op:
             assert r["status"] == 0, f"case {c['hdr']} refused: {r['message']}"
             yield c, r
-
-
-def _untouched(x):
-    return (np.ascontiguousarray(x).view(np.uint32) == FILL).all()
 
 
 def _t(x):

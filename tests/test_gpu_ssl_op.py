@@ -36,7 +36,6 @@ write or read past a row are now refused by WSP_CHECK and asserted here: attenti
 LayerNorm's ldx / ldo < D, and an add remap whose last group ends past ldadd.
 """
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -45,30 +44,25 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import op_runner  # noqa: E402
 import ssl_op_cases as cases  # noqa: E402
 import ssl_op_ref as ref  # noqa: E402
-from ssl_op_ref import DH, FILL, t64  # noqa: E402
+from op_runner import untouched as _untouched  # noqa: E402
+from ssl_op_ref import DH, t64  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RUNNER = os.path.join(ROOT, "tools", "ssl_run")
 MEASURED_ATTN_EXCESS = 0.0  # MI355X: largest excess over the allowance without e_exp, relative to 2 sum a |v|
 MEASURED_GATE_EXCESS = 0.0  # MI355X: the same for the gate, relative to (|t| + ga |grep|) / 4
 E_EXP = 4.0 * MEASURED_ATTN_EXCESS
 E_GATE = 4.0 * MEASURED_GATE_EXCESS
 assert E_EXP <= 1e-6 and E_GATE <= 1e-6
 SINGLES = ("ragged", "walk")  # ragged batches whose utterances also run as batches of one
-_RESULTS = {}
 
 
 @pytest.fixture(scope="module")
 def res(tmp_path_factory):
     """One runner process for all cases: dict key -> (case, result arrays)."""
-    if "r" in _RESULTS:
-        return _RESULTS["r"]
-    if not os.path.exists(RUNNER):
-        pytest.fail(f"{RUNNER} not built (run __graft_entry__.build())")
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     todo = []
     for c in cases.attention_cases(ncu):
@@ -81,15 +75,10 @@ def res(tmp_path_factory):
     for c, _ in cases.refused_cases():
         todo.append((c["name"], dict(c, pipe=1)))
     assert len(todo) <= 4096 and len({k for k, _ in todo}) == len(todo)
-    d = tmp_path_factory.mktemp("ssl_op")
-    fin, fout = str(d / "cases.bin"), str(d / "results.bin")
-    cases.write_cases(fin, [c for _, c in todo])
-    p = subprocess.run([RUNNER, fin, fout], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, f"runner status {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
+    results = op_runner.run("ssl_run", cases.MAGIC, [cases.op_case(c) for _, c in todo], tmp_path_factory.mktemp("ssl_op"))
     out = {"ncu": ncu}
-    for (key, c), r in zip(todo, cases.read_results(fout, len(todo))):
+    for (key, c), r in zip(todo, results):
         out[key] = (c, r)
-    _RESULTS["r"] = out
     return out
 
 
@@ -97,10 +86,6 @@ def _ran(res, key):
     c, r = res[key]
     assert r["status"] == 0, f"{key} refused: {r['message']}"
     return c, r["arrays"]
-
-
-def _untouched(x):
-    return bool((np.ascontiguousarray(x).view(np.uint32) == FILL).all())
 
 
 def _attn_out(res, name, pipe):

@@ -24,8 +24,6 @@ f32 rounding of phi, which the kernel's result then nearly fills).  The offset t
 exactly.
 """
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -33,9 +31,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RUNNER = os.path.join(ROOT, "tools", "xi_run")
-MAGIC_IN, MAGIC_OUT, FILL = 0x58505357, 0x52505357, 0x7FC5A5A5
+import op_runner  # noqa: E402
+from op_runner import FILL  # noqa: E402
+
+MAGIC = 0x58505357
 XI, OFFS = 1, 2
 
 pytestmark = pytest.mark.gpu
@@ -85,37 +84,10 @@ IDS = [_id(c) for c in CASES]
 
 @pytest.fixture(scope="module")
 def results(tmp_path_factory):
-    d = tmp_path_factory.mktemp("xi_op")
-    fin, fout = str(d / "cases.bin"), str(d / "results.bin")
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<III", MAGIC_IN, 1, len(CASES)))
-        for c in CASES:
-            f.write(struct.pack("<I8i", c["op"], *c["hdr"]))
-            for a in c["arrays"]:
-                a = np.ascontiguousarray(a)
-                assert a.dtype.itemsize == 4
-                f.write(struct.pack("<I", a.size))
-                f.write(a.tobytes())
-    p = subprocess.run([RUNNER, fin, fout], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, f"runner status {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}"
-    buf = open(fout, "rb").read()
-    magic, n = struct.unpack_from("<II", buf, 0)
-    assert magic == MAGIC_OUT and n == len(CASES)
-    pos, out = 8, []
-    for _ in range(n):
-        status, mlen = struct.unpack_from("<II", buf, pos)
-        pos += 8
-        msg = buf[pos:pos + mlen].decode()
-        pos += mlen
-        words = None
-        if status == 0:
-            (cnt,) = struct.unpack_from("<I", buf, pos)
-            pos += 4
-            words = np.frombuffer(buf, dtype=np.uint32, count=cnt, offset=pos).copy()
-            pos += 4 * cnt
-        out.append((status, msg, words))
-    assert pos == len(buf)
-    return out
+    """One runner process for all cases: (status, message, result words as uint32)."""
+    out = op_runner.run("xi_run", MAGIC, [(c["op"], c["hdr"], c["arrays"]) for c in CASES],
+                        tmp_path_factory.mktemp("xi_op"))
+    return [(r["status"], r["message"], r["arrays"][0].view(np.uint32) if r["status"] == 0 else None) for r in out]
 
 
 def xi_reference(c):

@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import op_runner  # noqa: E402
 import ssl_op_cases as cases  # noqa: E402
 import ssl_op_ref as ref  # noqa: E402
 from ssl_op_ref import DH, REL_MAX, REL_STRIDE, t64  # noqa: E402
@@ -437,5 +438,7 @@ def test_case_files_round_trip(tmp_path):
     cs = [dict(ATTN[0], pipe=1), dict(BY_NAME["bias_ragged"], pipe=0)] + cases.GATE_CASES[:1] + cases.POS_CASES[:1] \
         + cases.LN_CASES[-2:] + cases.CONV0_CASES[-1:] + [dict(c, pipe=1) for c, _ in cases.refused_cases()]
     p = tmp_path / "cases.bin"
-    cases.write_cases(str(p), cs)
-    assert p.stat().st_size > 12 + 68 * len(cs)
+    sent = [cases.op_case(c) for c in cs]
+    nh = op_runner.LAYOUT["ssl_run"][0]
+    op_runner.write_cases(str(p), cases.MAGIC, sent, nh)
+    assert p.stat().st_size == 12 + sum(4 + 4 * nh + sum(4 + 4 * np.size(a) for a in arrs) for _, _, arrs in sent)

@@ -1,26 +1,20 @@
 // Op-level runner for the implicit-GEMM conv kernels (tests/test_gpu_conv_gemm_op.py).
+// Launches the dispatchers of libwsp_hip.so (launch_conv_gemm, launch_conv_gemm_x3,
+// conv_gemm_x3_block_rows, launch_colsum_mean).  The float64 reference and the error bound live in
+// tests/conv_gemm_ref.py.  Weights arrive in torch layout and go through the project's own
+// pack::conv_kmajor / pack::split, so the packer is under test as well.  Framing, case and result
+// files: tools/op_runner.h.  Magic 'WSPC' (0x43505357).
 //
-//   conv_gemm_run <case file> <result file>
-//
-// Reads cases, launches each one through the SHIPPED dispatchers of libwsp_hip.so
-// (launch_conv_gemm, launch_conv_gemm_x3, conv_gemm_x3_block_rows, launch_colsum_mean) and
-// writes back every byte the launch could have touched.  It holds no reference arithmetic: the
-// float64 reference and the error bound live in tests/conv_gemm_ref.py.  Weights arrive in
-// torch layout and go through the project's own pack::conv_kmajor / pack::split, so the packer
-// is under test as well.  A second operator would be one more `op` code beside kOpConvGemm.
-//
-// Case file (little-endian; written by conv_gemm_ref.write_cases):
-//   u32 magic 'WSPC' (0x43505357), u32 version (1), u32 ncases, then per case
-//   u32 op                      1 = conv_gemm
-//   i32 hdr[kNH]                in this order:
+//   op 1  conv_gemm
+//   hdr (42 ints and one f32), in this order:
 //        variant (3..7; ignored for precision 0), precision (0 = f32 kernel, 1 = bf16x3), flags,
 //        lda[3], cseg[4], cin, taps, dil, pad, M, T, N, ldres, ldo, act, amode, role, conv2d,
 //        Fi, Ti, Fo, To, stride, kw, sc2d, gcols, gcin, nseg, lnmode, ln_parts,
 //        arows[3]  rows of A buffer i (the buffer holds arows[i] * lda[i] floats),
 //        aoff[3]   first float of the operand inside each row (a view into a wider buffer),
 //        B         utterances (rows of row_bias and of the column means)
-//   f32 ln_eps
-//   arrays, each as u32 count + count values, only where its flag bit is set, in this order:
+//        ln_eps    f32, in the header's last word
+//   arrays, only where the flag bit is set, in this order:
 //        bit 0..2  a[0..2]      f32 [arows][lda]
 //        (always)  w            f32 [N][cin][taps]   torch layout (2-D: [N][cin][kh][kw])
 //        bit 3     bias         f32 [N]
@@ -33,30 +27,24 @@
 //        bit 10    ln_in        f32 [M][ln_parts][2]
 //        bit 11    ln_cs        f32 [N]
 //        bit 12    ln_g, ln_b   f32 [N] each
-//   Every count is checked against the header, and the header against the rows / columns the
-//   kernels will read: a malformed case ends the run with status 2 before anything is launched.
+//   The header is checked against the rows / columns the kernels will read.
 //   K = cin * taps; Kp = K rounded up to 64.
-//
-// Result file: u32 magic 'WSPR' (0x52505357), u32 ncases, then per case
-//   u32 status (0 = ran, 1 = refused by a WSP_CHECK of the library), char tile[24], i32 block_rows,
-//   u32 count + message bytes (the refusal), and, when it ran,
-//   u32 count + f32 out [(M + 8)][ldo]  pre-filled with the NaN pattern 0x7FC5A5A5: guard rows
-//                                       and guard columns must come back untouched,
-//   u32 count + f32 means [B][N]        launch_colsum_mean of the partials (0 without bit 9),
-//   u32 count + f32 ln_out [M][N/128][2] (0 unless lnmode & 1).
-// `tile` names the kernel that served the launch: "g256" where wsp::x3::g256_supported takes the
-// operands under variant 7, else the tile launch_conv_gemm_x3 / launch_conv_gemm pick.
-// One line per case goes to stdout.  Any HIP error ends the process with status 3 at once.
-#include <hip/hip_runtime.h>
-
+//   results, always three:
+//        out [(M + 8)][ldo]   guard rows and guard columns must come back untouched,
+//        means [B][N]         launch_colsum_mean of the partials (empty without bit 9),
+//        ln_out [M][N/128][2] (empty unless lnmode & 1).
+//   own words of the result record (7): char tile[24], i32 block_rows, written for refused cases
+//   too.  `tile` names the kernel that served the launch: "g256" where wsp::x3::g256_supported takes
+//   the operands under variant 7, else the tile launch_conv_gemm_x3 / launch_conv_gemm pick;
+//   block_rows is 0 without bit 9.
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../wespeaker_hubert_amd/csrc/kernels.h"
 #include "../wespeaker_hubert_amd/csrc/pack.h"
+#include "op_runner.h"
 
 namespace wsp {
 namespace x3 {
@@ -68,8 +56,7 @@ using namespace wsp;
 
 namespace {
 
-constexpr uint32_t kMagicIn = 0x43505357u, kMagicOut = 0x52505357u, kVersion = 1, kOpConvGemm = 1;
-constexpr uint32_t kFill = 0x7FC5A5A5u;
+constexpr uint32_t kOpConvGemm = 1;
 enum {
   H_VARIANT, H_PRECISION, H_FLAGS, H_LDA0, H_LDA1, H_LDA2, H_CSEG0, H_CSEG1, H_CSEG2, H_CSEG3, H_CIN, H_TAPS,
   H_DIL, H_PAD, H_M, H_T, H_N, H_LDRES, H_LDO, H_ACT, H_AMODE, H_ROLE, H_CONV2D, H_FI, H_TI, H_FO, H_TO, H_STRIDE,
@@ -79,68 +66,6 @@ enum {
 enum {
   F_A0 = 1, F_A1 = 2, F_A2 = 4, F_BIAS = 8, F_ROWBIAS = 16, F_RES = 32, F_SCALE = 64, F_SEG = 128, F_ISEG = 256,
   F_COLSUM = 512, F_LNIN = 1024, F_LNCS = 2048, F_LNGB = 4096
-};
-
-[[noreturn]] void die(int status, const std::string& msg) {
-  std::fprintf(stderr, "conv_gemm_run: %s\n", msg.c_str());
-  std::fflush(stderr);
-  std::exit(status);
-}
-#define BAD(cond, msg)                                  \
-  do {                                                  \
-    if (!(cond)) die(2, std::string("bad case: ") + (msg)); \
-  } while (0)
-#define CK(x)                                                                                       \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) die(3, std::string(#x) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
-
-struct Reader {
-  FILE* f;
-  void raw(void* dst, size_t n) { BAD(std::fread(dst, 1, n, f) == n, "file too short"); }
-  uint32_t u32() {
-    uint32_t v;
-    raw(&v, 4);
-    return v;
-  }
-  template <typename T>
-  std::vector<T> arr(long long expect, const char* what) {
-    const uint32_t n = u32();
-    BAD((long long)n == expect, std::string(what) + ": count does not match the header");
-    std::vector<T> v(n);
-    if (n) raw(v.data(), (size_t)n * sizeof(T));
-    return v;
-  }
-};
-
-struct Writer {
-  FILE* f;
-  void raw(const void* src, size_t n) {
-    if (std::fwrite(src, 1, n, f) != n) die(2, "cannot write the result file");
-  }
-  void u32(uint32_t v) { raw(&v, 4); }
-  template <typename T>
-  void arr(const std::vector<T>& v) {
-    u32((uint32_t)v.size());
-    if (!v.empty()) raw(v.data(), v.size() * sizeof(T));
-  }
-};
-
-// device buffers of one case
-struct Pool {
-  std::vector<void*> ptrs;
-  template <typename T>
-  T* up(const std::vector<T>& v) {
-    void* d = nullptr;
-    CK(hipMalloc(&d, v.empty() ? sizeof(T) : v.size() * sizeof(T)));
-    ptrs.push_back(d);
-    if (!v.empty()) CK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return static_cast<T*>(d);
-  }
-  ~Pool() {
-    for (void* d : ptrs) (void)hipFree(d);
-  }
 };
 
 // The tile launch_conv_gemm_x3 picks for operands family 7 does not take (conv_gemm_x3.hip).
@@ -155,11 +80,13 @@ const char* x3_tile(const ConvGemmArgs& p, int variant) {
   return "256x128";
 }
 
-void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
-  int h[kNH];
-  in.raw(h, sizeof(h));
+void run_conv_gemm(Case& in) {
+  BAD(in.op == kOpConvGemm, "unknown operator");
+  const int* h = in.h;
+  Pool& pool = in.pool;
+  hipStream_t s = in.stream;
   float ln_eps;
-  in.raw(&ln_eps, 4);
+  std::memcpy(&ln_eps, &h[kNH], 4);
   const int flags = h[H_FLAGS], M = h[H_M], T = h[H_T], N = h[H_N], cin = h[H_CIN], taps = h[H_TAPS];
   const int ldo = h[H_LDO], B = h[H_B], nseg = h[H_NSEG];
   BAD(M > 0 && M < (1 << 20) && T > 0 && N > 0 && N <= 4096 && N % 32 == 0, "M / T / N out of range");
@@ -189,19 +116,19 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
   for (int i = 0; i < 3; ++i) {
     BAD(h[H_LDA0 + i] >= 0 && h[H_LDA0 + i] <= 8192 && h[H_AROWS0 + i] >= 0 && h[H_AROWS0 + i] < (1 << 21),
         "lda / arows out of range");
-    if (flags & (F_A0 << i)) a[i] = in.arr<float>((long long)h[H_AROWS0 + i] * h[H_LDA0 + i], "a");
+    if (flags & (F_A0 << i)) a[i] = in.f32((long long)h[H_AROWS0 + i] * h[H_LDA0 + i], "a");
   }
-  const std::vector<float> w = in.arr<float>((long long)N * cin * taps, "w");
+  const std::vector<float> w = in.f32((long long)N * cin * taps, "w");
   std::vector<float> bias, row_bias, res, scale, shift, ln_in, ln_cs, ln_g, ln_b;
-  if (flags & F_BIAS) bias = in.arr<float>(N, "bias");
-  if (flags & F_ROWBIAS) row_bias = in.arr<float>((long long)B * N, "row_bias");
+  if (flags & F_BIAS) bias = in.f32(N, "bias");
+  if (flags & F_ROWBIAS) row_bias = in.f32((long long)B * N, "row_bias");
   if (flags & F_RES) {
     BAD(h[H_LDRES] >= N && h[H_LDRES] <= 8192, "ldres < N");
-    res = in.arr<float>((long long)M * h[H_LDRES], "res");
+    res = in.f32((long long)M * h[H_LDRES], "res");
   }
   if (flags & F_SCALE) {
-    scale = in.arr<float>(N, "scale");
-    shift = in.arr<float>(N, "shift");
+    scale = in.f32(N, "scale");
+    shift = in.f32(N, "shift");
   }
   auto check_seg = [&](const std::vector<int>& v, const char* what) {
     BAD(v[0] == 0, std::string(what) + "[0] != 0");
@@ -209,23 +136,23 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
   };
   if (flags & F_SEG) {
     BAD(nseg >= 1 && nseg == B, "nseg != B");
-    seg = in.arr<int>(nseg + 1, "seg");
+    seg = in.i32(nseg + 1, "seg");
     check_seg(seg, "seg");
     BAD(seg[nseg] == M, "seg[nseg] != M");
   }
   if (flags & F_ISEG) {
     BAD(flags & F_SEG, "iseg without seg");
-    iseg = in.arr<int>(nseg + 1, "iseg");
+    iseg = in.i32(nseg + 1, "iseg");
     check_seg(iseg, "iseg");
   }
   if (flags & F_LNIN) {
     BAD(h[H_LNPARTS] >= 1 && h[H_LNPARTS] <= 8, "ln_parts out of range");
-    ln_in = in.arr<float>((long long)M * h[H_LNPARTS] * 2, "ln_in");
+    ln_in = in.f32((long long)M * h[H_LNPARTS] * 2, "ln_in");
   }
-  if (flags & F_LNCS) ln_cs = in.arr<float>(N, "ln_cs");
+  if (flags & F_LNCS) ln_cs = in.f32(N, "ln_cs");
   if (flags & F_LNGB) {
-    ln_g = in.arr<float>(N, "ln_g");
-    ln_b = in.arr<float>(N, "ln_b");
+    ln_g = in.f32(N, "ln_g");
+    ln_b = in.f32(N, "ln_b");
   }
   if (!c2d && !sc2d) {
     const int Ti = h[H_TI] > 0 ? h[H_TI] : T;
@@ -254,7 +181,6 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
   }
 
   // ---- pack and upload
-  Pool pool;
   const std::vector<float> packed = pack::conv_kmajor(w, N, cin, taps, Kp);
   std::vector<uint16_t> whi, wlo;
   pack::split(packed, whi, wlo);
@@ -285,14 +211,12 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
   if (flags & F_LNCS) p.ln_cs = pool.up(ln_cs);
   if (flags & F_LNGB) p.ln_g = pool.up(ln_g), p.ln_b = pool.up(ln_b);
 
-  std::vector<float> hout((size_t)(M + 8) * ldo), means, hln;
-  {
-    std::vector<uint32_t> fill(hout.size(), kFill);
-    p.out = reinterpret_cast<float*>(pool.up(fill));
-  }
+  const size_t nout = (size_t)(M + 8) * ldo;
+  p.out = pool.filled(nout);
   const int variant = h[H_VARIANT], precision = h[H_PRECISION];
   int bm = 0;
   double* dpart = nullptr;
+  size_t nln = 0;
   if (flags & F_COLSUM) {
     bm = precision ? conv_gemm_x3_block_rows(p, variant) : 128;
     BAD(bm == 128 || bm == 256, "unexpected block rows");
@@ -302,16 +226,14 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
   }
   if (p.lnmode & 1) {
     BAD(N % 128 == 0, "ln_out needs N % 128 == 0");
-    hln.assign((size_t)M * (N / 128) * 2, 0.f);
-    std::vector<uint32_t> fill(hln.size(), kFill);
-    p.ln_out = reinterpret_cast<float*>(pool.up(fill));
+    nln = (size_t)M * (N / 128) * 2;
+    p.ln_out = pool.filled(nln);
   }
 
   // ---- launch through the library's dispatchers
   const char* tile = "";
-  std::string refusal;
   float* dmeans = nullptr;
-  try {
+  in.guarded([&] {
     if (precision == 0) {
       tile = (conv_gemm_tile_for(N) == 0 && !p.gcols) ? "f32_128x128" : "f32_128x64";
       launch_conv_gemm(p, s);
@@ -320,67 +242,20 @@ void run_conv_gemm(Reader& in, Writer& out, int index, hipStream_t s) {
       launch_conv_gemm_x3(p, dhi, dlo, variant, s);
     }
     if (flags & F_COLSUM) {
-      means.assign((size_t)B * N, 0.f);
-      std::vector<uint32_t> fill(means.size(), kFill);
-      dmeans = reinterpret_cast<float*>(pool.up(fill));
+      dmeans = pool.filled((size_t)B * N);
       launch_colsum_mean(dpart, bm, T, B, N, dmeans, N, s);
     }
-  } catch (const InvalidArg& e) {
-    refusal = e.msg;
-  } catch (const HipError& e) {
-    die(3, e.where + ": " + hipGetErrorString(e.err));
-  } catch (...) {
-    die(3, "unknown exception from the library");
-  }
-  CK(hipStreamSynchronize(s));
-  CK(hipGetLastError());
-
-  char tname[24] = {0};
-  std::snprintf(tname, sizeof(tname), "%s", tile);
-  out.u32(refusal.empty() ? 0 : 1);
-  out.raw(tname, sizeof(tname));
-  out.u32((uint32_t)bm);
-  out.arr(std::vector<char>(refusal.begin(), refusal.end()));
-  if (!refusal.empty()) {
-    std::printf("case %d: refused: %s\n", index, refusal.c_str());
-    return;
-  }
-  CK(hipMemcpy(hout.data(), p.out, hout.size() * 4, hipMemcpyDeviceToHost));
-  if (dmeans) CK(hipMemcpy(means.data(), dmeans, means.size() * 4, hipMemcpyDeviceToHost));
-  if (!hln.empty()) CK(hipMemcpy(hln.data(), p.ln_out, hln.size() * 4, hipMemcpyDeviceToHost));
-  out.arr(hout);
-  out.arr(means);
-  out.arr(hln);
-  std::printf("case %d: precision %d variant %d M %d N %d K %d tile %s\n", index, precision, variant, M, N, K, tile);
+  });
+  std::snprintf(reinterpret_cast<char*>(in.own), 24, "%s", tile);
+  in.own[6] = (uint32_t)bm;
+  in.note = "precision " + std::to_string(precision) + " variant " + std::to_string(variant) + " M " + std::to_string(M) +
+            " N " + std::to_string(N) + " K " + std::to_string(K) + " tile " + tile;  // the stdout line
+  in.result(p.out, nout);
+  in.result(dmeans, dmeans ? (size_t)B * N : 0);
+  in.result(p.ln_out, nln);
 }
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc != 3) die(2, "usage: conv_gemm_run <case file> <result file>");
-  FILE* fi = std::fopen(argv[1], "rb");
-  if (!fi) die(2, std::string("cannot open ") + argv[1]);
-  FILE* fo = std::fopen(argv[2], "wb");
-  if (!fo) die(2, std::string("cannot open ") + argv[2]);
-  Reader in{fi};
-  Writer out{fo};
-  BAD(in.u32() == kMagicIn, "not a case file");
-  BAD(in.u32() == kVersion, "unknown case file version");
-  const uint32_t n = in.u32();
-  BAD(n >= 1 && n <= 4096, "case count out of range");
-  out.u32(kMagicOut);
-  out.u32(n);
-  hipStream_t s;
-  CK(hipStreamCreate(&s));
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t op = in.u32();
-    BAD(op == kOpConvGemm, "unknown operator");
-    run_conv_gemm(in, out, (int)i, s);
-    std::fflush(stdout);
-  }
-  BAD(std::fgetc(fi) == EOF, "trailing bytes after the last case");
-  CK(hipStreamDestroy(s));
-  std::fclose(fi);
-  if (std::fclose(fo) != 0) die(2, "cannot write the result file");
-  return 0;
-}
+static_assert(kNH + 1 == 43, "the header: kNH ints and ln_eps");
+int main(int argc, char** argv) { return op_runner_main(argc, argv, "conv_gemm_run", 0x43505357u, Layout{43, 7, 3}, run_conv_gemm); }

@@ -1,15 +1,10 @@
 // Op-level runner for the kernels only the HuBERT / WavLM front end uses (tests/test_gpu_ssl_op.py).
+// Launches launch_attn, launch_attn_gate, launch_hubert_pos_conv, launch_layernorm and
+// launch_hubert_conv0 of libwsp_hip.so, with pos_conv's weights packed by the library's own
+// pack::conv_kmajor / pack::split as the model packs them.  Framing, case and result files:
+// tools/op_runner.h.  Magic 'WSPS' (0x53505357).  Arrays are f32; the offset arrays seg / wseg /
+// oseg / fseg are i32.
 //
-//   ssl_run <case file> <result file>
-//
-// Reads cases and launches each one through the SHIPPED launchers of libwsp_hip.so (launch_attn,
-// launch_attn_gate, launch_hubert_pos_conv, launch_layernorm, launch_hubert_conv0), with pos_conv's
-// weights packed by the library's own pack::conv_kmajor / pack::split as the model packs them, then
-// writes back every byte the launch could have touched.  It holds no reference arithmetic.
-//
-// Case file (little-endian): u32 magic 'WSPS' (0x53505357), u32 version (1), u32 ncases, then per
-// case u32 op, i32 hdr[16] and the op's arrays, each as u32 count + count values (f32; the offset
-// arrays seg / wseg / oseg / fseg are i32):
 //   op 1  attention     hdr = B, T (longest utterance), H, dh, ldq, ldo, rows, nseg (0: uniform, else B),
 //                       pipe, has_bias
 //         arrays qkv [rows][ldq], (seg [B + 1]), (table [H][1560], gate [rows][H])
@@ -29,175 +24,88 @@
 //                       wrows (samples in all), orows (frames in all)
 //         arrays wav [wrows], w [512][10], gamma [512], beta [512], (wseg [B + 1], oseg [B + 1])
 //         results out [(orows + 8)][512]
-// Every count is checked against the header, and every offset array against the rows it indexes: a
-// malformed case ends the run with status 2 before anything is launched.
-//
-// Result file: u32 magic 'WSPR' (0x52505357), u32 ncases, then per case u32 status (0 = ran,
-// 1 = refused by a WSP_CHECK), u32 count + message bytes, and when it ran u32 narrays and the
-// result arrays (u32 count + f32), pre-filled with the NaN pattern 0x7FC5A5A5: guard rows and guard
-// columns must come back untouched.  Any HIP error ends the process with status 3 at once.
-#include <hip/hip_runtime.h>
-
+// Every offset array is checked against the rows it indexes.  Guard rows and guard columns must come
+// back untouched.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
 #include <vector>
 
 #include "../wespeaker_hubert_amd/csrc/attn.h"
 #include "../wespeaker_hubert_amd/csrc/kernels.h"
 #include "../wespeaker_hubert_amd/csrc/pack.h"
+#include "op_runner.h"
 
 using namespace wsp;
 
 namespace {
 
-constexpr uint32_t kMagicIn = 0x53505357u, kMagicOut = 0x52505357u, kVersion = 1, kFill = 0x7FC5A5A5u;
-constexpr int kNH = 16;
 constexpr long long kMaxRows = 1 << 20;
 
-[[noreturn]] void die(int status, const std::string& msg) {
-  std::fprintf(stderr, "ssl_run: %s\n", msg.c_str());
-  std::fflush(stderr);
-  std::exit(status);
-}
-#define BAD(cond, msg)                                      \
-  do {                                                      \
-    if (!(cond)) die(2, std::string("bad case: ") + (msg)); \
-  } while (0)
-#define CK(x)                                                                    \
-  do {                                                                           \
-    hipError_t e_ = (x);                                                         \
-    if (e_ != hipSuccess) die(3, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-struct Reader {
-  FILE* f;
-  void raw(void* dst, size_t n) { BAD(std::fread(dst, 1, n, f) == n, "file too short"); }
-  uint32_t u32() {
-    uint32_t v;
-    raw(&v, 4);
-    return v;
-  }
-  template <typename T>
-  std::vector<T> arr_of(long long expect, const char* what) {
-    static_assert(sizeof(T) == 4, "4-byte elements");
-    const uint32_t n = u32();
-    BAD((long long)n == expect, std::string(what) + ": count does not match the header");
-    std::vector<T> v(n);
-    if (n) raw(v.data(), (size_t)n * 4);
-    return v;
-  }
-  std::vector<float> arr(long long expect, const char* what) { return arr_of<float>(expect, what); }
-  // offsets of B utterances over `rows` rows: 0 = s[0] < s[1] < ... < s[B] = rows, each at most `longest`
-  std::vector<int> offsets(int B, long long rows, long long longest, const char* what) {
-    const std::vector<int> s = arr_of<int>((long long)B + 1, what);
-    BAD(s[0] == 0 && s[B] == rows, std::string(what) + ": offsets do not span the rows");
-    for (int b = 0; b < B; ++b)
-      BAD(s[b + 1] > s[b] && s[b + 1] - s[b] <= longest, std::string(what) + ": utterance length out of range");
-    return s;
-  }
-};
-
-struct Writer {
-  FILE* f;
-  void raw(const void* src, size_t n) {
-    if (std::fwrite(src, 1, n, f) != n) die(2, "cannot write the result file");
-  }
-  void u32(uint32_t v) { raw(&v, 4); }
-  void arr(const std::vector<float>& v) {
-    u32((uint32_t)v.size());
-    if (!v.empty()) raw(v.data(), v.size() * 4);
-  }
-};
-
-struct Pool {
-  std::vector<void*> ptrs;
-  template <typename T>
-  T* up(const std::vector<T>& v) {
-    void* d = nullptr;
-    CK(hipMalloc(&d, v.empty() ? sizeof(T) : v.size() * sizeof(T)));
-    ptrs.push_back(d);
-    if (!v.empty()) CK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return static_cast<T*>(d);
-  }
-  float* filled(size_t n) { return reinterpret_cast<float*>(up(std::vector<uint32_t>(n, kFill))); }
-  ~Pool() {
-    for (void* d : ptrs) (void)hipFree(d);
-  }
-};
-
-std::vector<float> down(const float* d, size_t n) {
-  std::vector<float> v(n);
-  if (n) CK(hipMemcpy(v.data(), d, n * 4, hipMemcpyDeviceToHost));
-  return v;
+// offsets of B utterances over `rows` rows: 0 = s[0] < s[1] < ... < s[B] = rows, each at most `longest`
+std::vector<int> offsets(Case& in, int B, long long rows, long long longest, const char* what) {
+  const std::vector<int> s = in.i32((long long)B + 1, what);
+  BAD(s[0] == 0 && s[B] == rows, std::string(what) + ": offsets do not span the rows");
+  for (int b = 0; b < B; ++b)
+    BAD(s[b + 1] > s[b] && s[b + 1] - s[b] <= longest, std::string(what) + ": utterance length out of range");
+  return s;
 }
 
-void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
-  const uint32_t op = in.u32();
-  int h[kNH];
-  in.raw(h, sizeof(h));
-  Pool pool;
+void run_case(Case& in) {
+  const uint32_t op = in.op;
+  Pool& pool = in.pool;
+  hipStream_t s = in.stream;
   float* d[2] = {nullptr, nullptr};
   size_t n[2] = {0, 0};
-  std::string refusal;
-  auto guarded = [&](auto&& launch) {
-    try {
-      launch();
-    } catch (const InvalidArg& e) {
-      refusal = e.msg;
-    } catch (const HipError& e) {
-      die(3, e.where + ": " + hipGetErrorString(e.err));
-    }
-  };
   if (op == 1) {
+    const int* h = in.h;
     const int B = h[0], T = h[1], H = h[2], dh = h[3], ldq = h[4], ldo = h[5], rows = h[6], nseg = h[7], pipe = h[8],
               has_bias = h[9];
     BAD(B > 0 && B <= 4096 && T > 0 && T <= 4096 && H > 0 && H <= 16 && rows > 0 && rows < kMaxRows, "shape out of range");
     BAD(dh > 0 && dh <= 64 && ldq >= 3 * H * 64 && ldq <= 8192 && ldo > 0 && ldo <= 8192, "bad strides");
     BAD((nseg == 0 && rows == B * T) || nseg == B, "rows / nseg do not match the batch");
     BAD((pipe == 0 || pipe == 1) && (has_bias == 0 || has_bias == 1), "bad pipe / bias flag");
-    const std::vector<float> qkv = in.arr((long long)rows * ldq, "qkv");
+    const std::vector<float> qkv = in.f32((long long)rows * ldq, "qkv");
     std::vector<int> seg;
-    if (nseg) seg = in.offsets(B, rows, T, "seg");
+    if (nseg) seg = offsets(in, B, rows, T, "seg");
     std::vector<float> table, gate;
     if (has_bias) {
-      table = in.arr((long long)H * kAttnRelStride, "table");
-      gate = in.arr((long long)rows * H, "gate");
+      table = in.f32((long long)H * kAttnRelStride, "table");
+      gate = in.f32((long long)rows * H, "gate");
     }
     n[0] = (size_t)(rows + 8) * std::max(ldo, H * 64);  // a row stride the launcher must refuse stays in bounds
     d[0] = pool.filled(n[0]);
-    guarded([&] {
+    in.guarded([&] {
       AttnBias ab;
       if (has_bias) ab.table = pool.up(table), ab.gate = pool.up(gate);
       launch_attn(pool.up(qkv), ldq, d[0], ldo, B, T, H, dh, s, nseg ? pool.up(seg) : nullptr, pipe,
                   has_bias ? &ab : nullptr);
     });
   } else if (op == 2) {
+    const int* h = in.h;
     const int rows = h[0], H = h[1], ldx = h[2];
     BAD(rows > 0 && rows < kMaxRows && H > 0 && H <= 16 && ldx >= H * 64 && ldx <= 8192, "shape out of range");
-    const std::vector<float> x = in.arr((long long)rows * ldx, "x"), w = in.arr(130 + H, "w");
+    const std::vector<float> x = in.f32((long long)rows * ldx, "x"), w = in.f32(130 + H, "w");
     n[0] = (size_t)(rows + 8) * H;
     d[0] = pool.filled(n[0]);
-    guarded([&] { launch_attn_gate(pool.up(x), ldx, rows, H, pool.up(w), d[0], s); });
+    in.guarded([&] { launch_attn_gate(pool.up(x), ldx, rows, H, pool.up(w), d[0], s); });
   } else if (op == 3) {
+    const int* h = in.h;
     const int B = h[0], maxT = h[1], M = h[2], ldx = h[3], ldo = h[4], gout = h[5];
     constexpr int kG = 16, kCin = 48, kTaps = 128, kK = kCin * kTaps;
     BAD(B > 0 && B <= 4096 && maxT > 0 && M > 0 && M < kMaxRows, "shape out of range");
     BAD(ldx >= kG * kCin && ldx <= 8192 && gout >= kCin && gout <= 128 && ldo >= kG * gout && ldo <= 8192, "bad strides");
-    const std::vector<float> x = in.arr((long long)M * ldx, "x");
-    const std::vector<int> seg = in.offsets(B, M, maxT, "seg");
-    const std::vector<float> w = in.arr((long long)kG * gout * kK, "w"), bias = in.arr(kG * gout, "bias");
+    const std::vector<float> x = in.f32((long long)M * ldx, "x");
+    const std::vector<int> seg = offsets(in, B, M, maxT, "seg");
+    const std::vector<float> w = in.f32((long long)kG * gout * kK, "w"), bias = in.f32(kG * gout, "bias");
     n[0] = (size_t)(M + 8) * ldo;
     d[0] = pool.filled(n[0]);
-    guarded([&] {
+    in.guarded([&] {
       std::vector<uint16_t> hi, lo;
       pack::split(pack::conv_kmajor(w, kG * gout, kCin, kTaps, kK), hi, lo);
       launch_hubert_pos_conv(pool.up(x), ldx, pool.up(seg), B, maxT, M, pool.up(hi), pool.up(lo), kK, gout,
                              pool.up(bias), d[0], ldo, s);
     });
   } else if (op == 4) {
+    const int* h = in.h;
     const int M = h[0], D = h[1], ldx = h[2], ldo = h[3], has_add = h[4], ldadd = h[5], gin = h[6], gout = h[7],
               has_feat = h[8], feat_init = h[9], T = h[10], Tout = h[11], nseg = h[12], frows = h[13];
     BAD(M > 0 && M < kMaxRows && D > 0 && D <= 1024 && ldx > 0 && ldx <= 8192 && ldo > 0 && ldo <= 8192,
@@ -211,16 +119,16 @@ void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
     } else {
       BAD(nseg == 0 && frows == 0, "segments without a featurizer");
     }
-    std::vector<float> x = in.arr((long long)M * ldx, "x");
+    std::vector<float> x = in.f32((long long)M * ldx, "x");
     std::vector<float> add, prior;
-    if (has_add) add = in.arr((long long)M * ldadd, "add");
+    if (has_add) add = in.f32((long long)M * ldadd, "add");
     x.resize(x.size() + slack, 0.f);
     if (has_add) add.resize(add.size() + slack, 0.f);
-    const std::vector<float> gamma = in.arr(D, "gamma"), beta = in.arr(D, "beta"), params = in.arr(2, "params");
+    const std::vector<float> gamma = in.f32(D, "gamma"), beta = in.f32(D, "beta"), params = in.f32(2, "params");
     std::vector<int> seg, fseg;
     if (nseg) {
-      seg = in.offsets(nseg, M, M, "seg");
-      fseg = in.offsets(nseg, frows, frows, "fseg");
+      seg = offsets(in, nseg, M, M, "seg");
+      fseg = offsets(in, nseg, frows, frows, "fseg");
     }
     n[0] = (size_t)(M + 8) * std::max(ldo, D);
     d[0] = pool.filled(n[0]);
@@ -228,11 +136,11 @@ void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
       n[1] = (size_t)(frows + 8) * D;
       d[1] = pool.filled(n[1]);
       if (!feat_init) {
-        prior = in.arr((long long)frows * D, "feat");
+        prior = in.f32((long long)frows * D, "feat");
         CK(hipMemcpy(d[1], prior.data(), prior.size() * 4, hipMemcpyHostToDevice));
       }
     }
-    guarded([&] {
+    in.guarded([&] {
       LayerNormArgs a{};
       a.x = pool.up(x), a.ldx = ldx;
       if (has_add) a.add = pool.up(add), a.ldadd = ldadd, a.gin = gin, a.gout = gout;
@@ -245,6 +153,7 @@ void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
       launch_layernorm(a, s);
     });
   } else if (op == 5) {
+    const int* h = in.h;
     const int B = h[0], N = h[1], ldw = h[2], T0 = h[3], nseg = h[4], wrows = h[5], orows = h[6];
     BAD(B > 0 && B <= 4096 && T0 > 0 && wrows > 0 && wrows < (1 << 24) && orows > 0 && orows < kMaxRows,
         "shape out of range");
@@ -252,16 +161,16 @@ void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
       BAD(nseg == B, "nseg does not match the batch");
     else
       BAD(N > 0 && ldw >= N && wrows == (long long)B * ldw && orows == (long long)B * T0, "bad uniform batch");
-    const std::vector<float> wav = in.arr(wrows, "wav"), w = in.arr(512 * 10, "w"), gamma = in.arr(512, "gamma"),
-                             beta = in.arr(512, "beta");
+    const std::vector<float> wav = in.f32(wrows, "wav"), w = in.f32(512 * 10, "w"), gamma = in.f32(512, "gamma"),
+                             beta = in.f32(512, "beta");
     std::vector<int> wseg, oseg;
     if (nseg) {
-      wseg = in.offsets(B, wrows, wrows, "wseg");
-      oseg = in.offsets(B, orows, T0, "oseg");
+      wseg = offsets(in, B, wrows, wrows, "wseg");
+      oseg = offsets(in, B, orows, T0, "oseg");
     }
     n[0] = (size_t)(orows + 8) * 512;
     d[0] = pool.filled(n[0]);
-    guarded([&] {
+    in.guarded([&] {
       double* stats = pool.up(std::vector<double>(hubert_conv0_stats_doubles(B, T0), 0.0));
       launch_hubert_conv0(pool.up(wav), B, N, ldw, T0, pool.up(w), pool.up(gamma), pool.up(beta), stats, d[0], s,
                           nseg ? pool.up(wseg) : nullptr, nseg ? pool.up(oseg) : nullptr);
@@ -269,46 +178,10 @@ void run_case(Reader& in, Writer& out, int index, hipStream_t s) {
   } else {
     BAD(false, "unknown operator");
   }
-  CK(hipStreamSynchronize(s));
-  CK(hipGetLastError());
-  out.u32(refusal.empty() ? 0 : 1);
-  out.u32((uint32_t)refusal.size());
-  out.raw(refusal.data(), refusal.size());
-  if (!refusal.empty()) {
-    std::printf("case %d: op %u refused: %s\n", index, op, refusal.c_str());
-    return;
-  }
-  const uint32_t na = d[1] ? 2 : 1;
-  out.u32(na);
-  for (uint32_t i = 0; i < na; ++i) out.arr(down(d[i], n[i]));
-  std::printf("case %d: op %u hdr %d %d %d %d %d %d %d %d\n", index, op, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+  in.result(d[0], n[0]);
+  if (d[1]) in.result(d[1], n[1]);
 }
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc != 3) die(2, "usage: ssl_run <case file> <result file>");
-  FILE* fi = std::fopen(argv[1], "rb");
-  if (!fi) die(2, std::string("cannot open ") + argv[1]);
-  FILE* fo = std::fopen(argv[2], "wb");
-  if (!fo) die(2, std::string("cannot open ") + argv[2]);
-  Reader in{fi};
-  Writer out{fo};
-  BAD(in.u32() == kMagicIn, "not a case file");
-  BAD(in.u32() == kVersion, "unknown case file version");
-  const uint32_t n = in.u32();
-  BAD(n >= 1 && n <= 4096, "case count out of range");
-  out.u32(kMagicOut);
-  out.u32(n);
-  hipStream_t s;
-  CK(hipStreamCreate(&s));
-  for (uint32_t i = 0; i < n; ++i) {
-    run_case(in, out, (int)i, s);
-    std::fflush(stdout);
-  }
-  BAD(std::fgetc(fi) == EOF, "trailing bytes after the last case");
-  CK(hipStreamDestroy(s));
-  std::fclose(fi);
-  if (std::fclose(fo) != 0) die(2, "cannot write the result file");
-  return 0;
-}
+int main(int argc, char** argv) { return op_runner_main(argc, argv, "ssl_run", 0x53505357u, Layout{16, 0, 0}, run_case); }

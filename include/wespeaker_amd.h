@@ -227,6 +227,12 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *                  splits its A fragments (default; bit-identical to 0).  Effective at precision 1,
  *                  x3_variant 7 on uniform batches of T >= 256 frames; ragged or shorter batches
  *                  and the other kernels keep the gate pass.  0 = the gate pass throughout
+ *   "seam_fold"    ECAPA-TDNN: 1 = the output of the first two SE-Res2Blocks, x + gate * conv3
+ *                  output, is formed by the next block's first 1x1 conv as it stages its input and
+ *                  written on the way, so the residual pass is no launch of its own (default;
+ *                  bit-identical to 0).  Effective under gate_fold's conditions (precision 1,
+ *                  x3_variant 7, uniform batches of T >= 256 frames); everything else keeps the
+ *                  residual pass.  0 = the residual pass throughout
  *   "cam_fused"    CAMPPlus: 1 (default) = the dense layers' BatchNorm + ReLU inside the 1x1
  *                  GEMM's A prologue; 0 = an elementwise pass of its own into scratch (A/B
  *                  runs only; bit-identical)

@@ -11,6 +11,12 @@
 // segment multiplied by a per-utterance gate as its fragments are read) against residual_scale<false>
 // followed by the ungated instance, bit for bit, on 3 utterances of 300 frames (a tile straddling
 // two utterances, a partial last tile).
+// Case seam (by name only): the seam kernel (conv_gemm_x3_t7.hip: A = x + g h formed while A is
+// staged and stored on the way) at M = 3 x 300, N = K = 512 and 1024, in both store forms: (a) the
+// sum it stored against residual_scale<true>'s, over a NaN-filled buffer with guard rows behind row
+// M that must stay untouched; (b) its GEMM output against family 7 on that stored sum.  Case
+// seam_time: the same at M = 256 x 498, N = K = 1024, then interleaved timing rounds of
+// residual_scale<true> + family 7 against the seam kernel (round 0 is the warm-up).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -224,6 +230,77 @@ int main(int argc, char** argv) {
     std::printf("gate_seg   family 7 gated vs residual_scale + family 7: %llu of %zu outputs differ\n", d, c.out_words);
     std::printf(d ? "MISMATCH in 1 comparisons\n" : "all families bit-identical\n");
     return d ? 1 : 0;
+  }
+  if (which == "seam" || which == "seam_time") {
+    // seam: 3 x 300 rows at C = 512 and 1024, both store forms, bit for bit; seam_time: the C2 shape
+    // (256 x 498 rows, C = 1024), interleaved rounds against the two launches the seam replaces
+    const bool timing = which == "seam_time";
+    const int B = timing ? 256 : 3, T = timing ? 498 : 300, M = B * T, guard = 8;
+    for (int C : timing ? std::vector<int>{1024} : std::vector<int>{512, 1024}) {
+      Case c = make("seam", B, T, T, 1, C, 1, 1, 0, C, kActRelu, true, false, false, false, 1, nullptr);
+      const size_t words = (size_t)M * C, gwords = (size_t)guard * C;
+      float* hb = dfill(words, 41, -1.f, 1.f, 1);
+      float* gate = dfill((size_t)B * C, 31, 0.f, 1.f, 0);
+      float *sum_ref, *sum_got, *gref, *ref, *got;
+      CK(hipMalloc(&sum_ref, words * 4));
+      CK(hipMalloc(&sum_got, (words + gwords) * 4));
+      CK(hipMalloc(&gref, gwords * 4));
+      CK(hipMalloc(&ref, c.out_words * 4));
+      CK(hipMalloc(&got, c.out_words * 4));
+      CK(hipMemset(gref, 0xff, gwords * 4));
+      CK(hipMemset(ref, 0xff, c.out_words * 4));
+      ConvGemmArgs qr = c.g;  // family 7 on the materialised sum
+      qr.a[0] = qr.a[1] = qr.a[2] = sum_ref;
+      qr.out = ref;
+      ConvGemmArgs qs = c.g;  // the seam kernel
+      qs.seam_h = hb;
+      qs.ld_seam_h = C;
+      qs.gate = gate;
+      qs.ldg = C;
+      qs.seam_out = sum_got;
+      qs.ld_seam_out = C;
+      qs.out = got;
+      if (!x3::seam_supported(qs)) { std::fprintf(stderr, "seam: the kernel does not take these operands\n"); return 2; }
+      launch_residual_scale(c.g.a[0], hb, gate, sum_ref, B, T, C, s);
+      x3::t_g256(qr, c.whi, c.wlo, s);
+      for (int bal = 1; bal >= 0; --bal) {
+        CK(hipMemsetAsync(sum_got, 0xff, (words + gwords) * 4, s));  // a NaN pattern, guard rows behind row M
+        CK(hipMemsetAsync(got, 0xee, c.out_words * 4, s));
+        x3::t_seam(qs, c.whi, c.wlo, s, bal != 0);
+        CK(hipStreamSynchronize(s));
+        const unsigned long long da = ndiff(sum_ref, sum_got, words), dg = ndiff(gref, sum_got + words, gwords);
+        const unsigned long long db = ndiff(ref, got, c.out_words);
+        const char* form = bal ? "balanced" : "first-block";
+        std::printf("seam C=%d %s sum vs residual_scale<true>: %llu of %zu words differ, %llu of %zu guard words touched\n",
+                    C, form, da, words, dg, gwords);
+        std::printf("seam C=%d %s GEMM vs family 7 on the stored sum: %llu of %zu outputs differ\n", C, form, db,
+                    c.out_words);
+        bad += (da != 0) + (dg != 0) + (db != 0);
+      }
+      if (timing) {
+        auto timed = [&](auto&& f) {
+          CK(hipEventRecord(e0, s));
+          for (int r = 0; r < reps; ++r) f();
+          CK(hipEventRecord(e1, s));
+          CK(hipEventSynchronize(e1));
+          float ms = 0;
+          CK(hipEventElapsedTime(&ms, e0, e1));
+          return ms / reps;
+        };
+        for (int round = 0; round < 4; ++round) {  // round 0 is the warm-up
+          const float t_rs = timed([&] { launch_residual_scale(c.g.a[0], hb, gate, sum_ref, B, T, C, s); });
+          const float t_g = timed([&] { x3::t_g256(qr, c.whi, c.wlo, s); });
+          const float t_b = timed([&] { x3::t_seam(qs, c.whi, c.wlo, s, true); });
+          const float t_f = timed([&] { x3::t_seam(qs, c.whi, c.wlo, s, false); });
+          std::printf("round %d%s M=%d N=K=%d residual_scale %.4f + family 7 %.4f = %.4f ms | seam balanced %.4f ms, first-block %.4f ms\n",
+                      round, round ? "" : " (warm-up)", M, C, t_rs, t_g, t_rs + t_g, t_b, t_f);
+          std::fflush(stdout);
+        }
+      }
+      for (float* q : {hb, gate, sum_ref, sum_got, gref, ref, got}) CK(hipFree(q));
+    }
+    std::printf(bad ? "MISMATCH in %d comparisons\n" : "all families bit-identical\n", bad);
+    return bad ? 1 : 0;
   }
   for (const Case& c : cases) {
     std::vector<float*> out(8, nullptr);

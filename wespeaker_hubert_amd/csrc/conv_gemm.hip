@@ -156,8 +156,8 @@ void launch_conv_gemm(const ConvGemmArgs& args, hipStream_t s) {
   WSP_CHECK(!p.conv2d && p.N % 64 == 0, "conv_gemm (f32): 1-D convs with N % 64 == 0 only");
   WSP_CHECK(!p.gcols || p.gcols % 64 == 0, "conv_gemm (f32): grouped columns must be a multiple of 64");
   // operands only bf16x3 tile family 7 implements: this kernel would read them as a plain 1x1 GEMM
-  WSP_CHECK(!p.sc2d && !p.lnmode && !p.gate,
-            "conv_gemm (f32): conv3 + shortcut, the LayerNorm fold and the gated A tail run on tile family 7");
+  WSP_CHECK(!p.sc2d && !p.lnmode && !p.gate && !p.seam_h && !p.seam_out,
+            "conv_gemm (f32): conv3 + shortcut, the LayerNorm fold, the gated A tail and the seam run on tile family 7");
   if (conv_gemm_tile_for(p.N) == 0 && !p.gcols)
     launch_tile<2, 2, 2, 2>(p, s);
   else

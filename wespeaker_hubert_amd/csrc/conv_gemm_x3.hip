@@ -56,6 +56,10 @@ bool conv_gemm_x3_gate_ok(const ConvGemmArgs& args, int variant) {
   return variant == 7 && args.gate && x3::g256_gate_supported(normalized(args));
 }
 
+bool conv_gemm_x3_seam_ok(const ConvGemmArgs& args, int variant) {
+  return variant == 7 && args.seam_h && x3::seam_supported(normalized(args));
+}
+
 void launch_conv_gemm_x3(const ConvGemmArgs& args, const void* whi, const void* wlo, int variant,
                          hipStream_t s) {
   const ConvGemmArgs p = normalized(args);
@@ -70,6 +74,12 @@ void launch_conv_gemm_x3(const ConvGemmArgs& args, const void* whi, const void* 
   const __bf16* h = static_cast<const __bf16*>(whi);
   const __bf16* l = static_cast<const __bf16*>(wlo);
   x3::TileFn f;
+  if (p.seam_h || p.seam_out) {  // the SE-Res2Block seam: A = x + g h, written out on the way (conv_gemm_x3_t7.hip)
+    WSP_CHECK(variant == 7 && x3::seam_supported(p),
+              "conv_gemm_x3: the seam runs on tile family 7 only (conv_gemm_x3_seam_ok)");
+    x3::t_seam(p, h, l, s);
+    return;
+  }
   WSP_CHECK(!p.lnmode || (variant == 7 && x3::g256_supported(p)),
             "conv_gemm_x3: the LayerNorm fold runs on tile family 7 only");
   WSP_CHECK(!p.sc2d || (variant == 7 && x3::g256_supported(p)),

@@ -363,6 +363,10 @@ void t_4x2_2x4_mf16(const ConvGemmArgs&, const __bf16*, const __bf16*, hipStream
 bool g256_supported(const ConvGemmArgs&);                                              // v7 operands
 bool g256_gate_supported(const ConvGemmArgs&);                                         // v7 with a gated A tail
 void t_g256(const ConvGemmArgs&, const __bf16*, const __bf16*, hipStream_t);         // v6 by LDS-DMA (v7)
+bool seam_supported(const ConvGemmArgs&);                                              // v7 with A = x + g h
+// the seam kernel (conv_gemm_x3_t7.hip); balanced = false: the row tile's first block stores every
+// k-tile of the sum (the measured alternative; the library launches the balanced form)
+void t_seam(const ConvGemmArgs&, const __bf16*, const __bf16*, hipStream_t, bool balanced = true);
 }  // namespace x3
 
 }  // namespace wsp

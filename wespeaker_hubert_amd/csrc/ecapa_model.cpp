@@ -6,7 +6,9 @@
 //           Res2 chain i=0..6: conv_k3(h1_i (+ h2_{i-1})) -> h2_i  (7 GEMMs)
 //           c3 (1x1) over cat(h2_0..6, h1_7)             -> h3   (no copy)
 //           SE: frame mean -> FC relu -> FC sigmoid -> x_{L} + h3 * g
-//           (the last block: g4 * h3 alone, or with gate_fold nothing — conv reads h3 and g4)
+//           (the last block: g4 * h3 alone, or with gate_fold nothing — conv reads h3 and g4;
+//           the first two with seam_fold: the next block's c1 forms the sum as it stages its A
+//           operand and writes it on the way — no pass of its own)
 //   conv    1x1 over cat(x2, x3, x4) (no copy), ReLU      -> xp   [M][1536]
 //   ASTP    [GLOB: frame mean/std -> per-utterance bias]  -> tanh(W1 xp) -> W2
 //           -> online-softmax attentive mean/std          -> [B][3072]
@@ -311,11 +313,23 @@ void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float*
   }
 
   gemm("layer1", layer1, feats, feat_dim, x[1], C, M, T, 1, 2, kActRelu, s, seg, B);
+  // seam_fold: the previous block left its output unwritten — gseam is this block's c1 with
+  // A = x + g (.) h3 (ConvGemmArgs::seam_h), which also stores that sum to this block's xin
+  ConvGemmArgs gseam{};
+  bool seam = false;
   for (int li = 0; li < 3; ++li) {
     const Block& b = blk[li];
     const int dil = li + 2;
     const float* xin = x[li + 1];
-    gemm("conv1x1_CxC", b.c1, xin, C, h1, C, M, T, 1, 0, kActRelu, s, seg, B, nullptr, true, 1);
+    if (seam) {
+      // one launch, both jobs: the block output it materialises (se.scale) and the C x C GEMM
+      run("se.scale", 0, s, [&] {
+        run("seam", 0, s, [&] { run("conv1x1_CxC", 2.0 * M * C * C, s, [&] { launch(gseam, b.c1, s); }); });
+      });
+      seam = false;
+    } else {
+      gemm("conv1x1_CxC", b.c1, xin, C, h1, C, M, T, 1, 0, kActRelu, s, seg, B, nullptr, true, 1);
+    }
     if (opt.precision == 1 && opt.res2_fused && b.r2w) {
       // the whole chain in one launch (res2_chain.hip)
       Res2Args r{};
@@ -369,6 +383,23 @@ void Ecapa::forward_chunk(const float* feats, int B, int T, float* embed, float*
     // cat_gate: the last block stores only g4 * h3 (conv_cat adds out3 through its weights);
     // gate_fold: not even that — conv_cat reads h3 and the gate (x[4] stays unwritten)
     if (li == 2 && fold) continue;
+    if (li < 2 && opt.seam_fold && opt.precision == 1) {
+      ConvGemmArgs g{};
+      one_operand(g, xin, C, C);
+      g.role = 1;
+      g.seam_h = h3;
+      g.ld_seam_h = C;
+      g.gate = W.gate;
+      g.ldg = C;
+      g.seam_out = x[li + 2];
+      g.ld_seam_out = C;
+      fill(g, blk[li + 1].c1, M, T, 1, 0, h1, C, kActRelu, nullptr, true, seg, B);
+      seam = conv_gemm_x3_seam_ok(g, opt.x3_variant);
+      if (seam) {
+        gseam = g;
+        continue;
+      }
+    }
     run("se.scale", 0, s, [&] {
       launch_residual_scale(opt.cat_gate && li == 2 ? nullptr : xin, h3, W.gate, x[li + 2], B, T, C, s, seg, M);
     });

@@ -94,6 +94,16 @@ struct ConvGemmArgs {
   // other kernel refuses a non-null gate.
   const float* gate;
   int ldg, gate_k0;
+  // SE-Res2Block seam (x3 tile family 7, conv_gemm_x3_t7.hip; same batch preconditions as the
+  // gated tail): A(m, k) = a[0](m, k) + gate[m / T][k] * seam_h(m, k) — fma(h, g, x), the value
+  // residual_scale<true> stores — formed while A is staged, and written once to seam_out
+  // [M][ld_seam_out] on the way (the block output x_{L+1}; the blocks of a row tile share its
+  // k-tiles out between them).  The gate spans all of K (gate_k0 = 0).  null = a plain GEMM.
+  // conv_gemm_x3_seam_ok() tells whether a launch takes it; every other kernel refuses it.
+  const float* seam_h;
+  int ld_seam_h;
+  float* seam_out;
+  int ld_seam_out;
 };
 
 // Fills the 1-D defaults (stride 1, Ti = T) of a zero-initialised ConvGemmArgs.
@@ -120,6 +130,8 @@ void launch_conv_gemm_x3(const ConvGemmArgs& p, const void* whi, const void* wlo
                          hipStream_t s);
 // whether launch_conv_gemm_x3(p, ., ., variant) takes p.gate (p filled as for the launch)
 bool conv_gemm_x3_gate_ok(const ConvGemmArgs& p, int variant);
+// whether launch_conv_gemm_x3(p, ., ., variant) takes p.seam_h / p.seam_out (the seam kernel)
+bool conv_gemm_x3_seam_ok(const ConvGemmArgs& p, int variant);
 
 
 // tile: 0 = 128x128 block (N % 128 == 0), 1 = 128x64 block (N % 64 == 0)

@@ -306,6 +306,7 @@ const Opt kOpts[] = {
     {"ib_fused", &I::ib_fused, 0, 1, kNoHole, "ib_fused must be 0 (conv1, depthwise conv, conv3) or 1 (conv1, fused tail)"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
     {"gate_fold", &I::gate_fold, 0, 1, kNoHole, "gate_fold must be 0 or 1"},
+    {"seam_fold", &I::seam_fold, 0, 1, kNoHole, "seam_fold must be 0 or 1"},
     {"res_prefetch", &I::res_prefetch, 0, 1, kNoHole, "res_prefetch must be 0 or 1"},
     {"res_tail", &I::res_tail, 0, 2, kNoHole, "res_tail must be 0 (off), 1 (tail + next conv1) or 2 (tail alone)"},
     {"sc_fuse", &I::sc_fuse, 0, 3, kNoHole, "sc_fuse must be 0 .. 3 (bit 0: one GEMM, bit 1: in the tail)"},

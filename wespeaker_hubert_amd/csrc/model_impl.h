@@ -128,6 +128,11 @@ struct Options {
   // written or read.  Effective where the GEMM takes a gate (bf16x3 tile family 7 on uniform
   // batches with T >= 256); everything else keeps the gate pass
   int gate_fold = 1;
+  // the first two blocks' x + g (.) h3 is formed by the next block's c1 as it stages its A operand
+  // (ConvGemmArgs::seam_h, conv_gemm_x3_t7.hip) and written on the way: the residual pass is no
+  // launch of its own.  Effective where the GEMM takes it (bf16x3 tile family 7 on uniform batches
+  // with T >= 256); everything else keeps the pass
+  int seam_fold = 1;
   // 0: linear2 GEMM + separate pooling kernel; 1: astp_fused.hip (256 channels per block, att
   // chunks two ahead in an LDS-DMA ring, W2 in VGPRs: C2 0.465 -> 0.31 ms)
   int astp_fused = 1;

@@ -20,7 +20,8 @@ FILL = 0x7FC5A5A5  # the NaN pattern result buffers are pre-filled with
 # Each runner's Layout, as the last line of its tools/<name>.cpp gives it: header ints of a case, words of
 # the runner's own in a result record, result arrays of a case that ran (None: their number is in the file).
 LAYOUT = {"conv_gemm_run": (43, 7, 3), "cam_dense_run": (8, 0, 2), "eres2net_run": (16, 0, 1),
-          "gemini_run": (16, 0, 1), "ssl_run": (16, 0, None), "xi_run": (8, 0, 1)}
+          "gemini_run": (16, 0, 1), "ssl_run": (16, 0, None), "xi_run": (8, 0, 1),
+          "ecapa_run": (16, 2, None)}
 
 
 def untouched(x):

@@ -262,8 +262,9 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
   bf16x8 ah[2], al[2], bh[4], bl[4];
   // gated tiles (AM 4): gp = this lane's 8 gate values of the tile in utterance slot 0 (the
   // utterance of the block's first row); rows from g_nb on belong to slot 1, g_slot bytes further
+  // (the gate tail rounded up to whole 1-KB DMA pieces: a tail of 128 or 384 columns ends inside one)
   const int g_nb = GATE ? min((m0 / p.T + 1) * p.T, p.M) - m0 : 0;
-  const int g_slot = GATE ? (p.K - p.gate_k0) * 4 : 0;
+  const int g_slot = GATE ? ((p.K - p.gate_k0) * 4 + 1023) & ~1023 : 0;
   auto rdA = [&](auto gated, const unsigned char* st, int ih, const unsigned char* gp = nullptr) {
     // fp32 rows -> bf16 hi / lo fragments (no contraction: the gated product is rounded to fp32
     // before the lo term's subtraction, as the stored g * h was)
@@ -316,15 +317,17 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_g(const ConvGemmArgs p, cons
     // the gate rows of utterances m0 / T and m0 / T + 1 (zeros past the batch) -> LDS behind the
     // stages, slot u at u * g_slot: 1-KB wave pieces issued ahead of tile 0's DMAs, so the first
     // counted wait below covers them (waves with no piece only have fewer operations outstanding)
-    const int ppu = g_slot >> 10, b0 = m0 / p.T;  // pieces per utterance (g_slot % 1024 == 0)
+    const int ppu = g_slot >> 10, b0 = m0 / p.T;  // pieces per utterance; the last one may be partly past the tail
+    const int gk = p.K - p.gate_k0;
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(p.gate);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // 2 g_slot <= 32 KB: at most 4 pieces per wave
       const int q = 8 * i + wave;
       if (q >= 2 * ppu) break;
       const int u = q >= ppu ? 1 : 0;
-      const bool ok = (b0 + u) * p.T < p.M;
-      g_dma(rg, smem + 2 * kGStage + q * 1024, ok ? ((b0 + u) * p.ldg + (q - u * ppu) * 256 + lane * 4) * 4 : kOOB);
+      const int gc = (q - u * ppu) * 256 + lane * 4;  // this lane's 4 gate columns
+      const bool ok = (b0 + u) * p.T < p.M && gc < gk;
+      g_dma(rg, smem + 2 * kGStage + q * 1024, ok ? ((b0 + u) * p.ldg + gc) * 4 : kOOB);
     }
   }
   dma(0, 0);
@@ -406,7 +409,8 @@ bool g256_supported(const ConvGemmArgs& p) {
 
 // The gated A tail (AM 4): a dense 1x1 GEMM on uniform k-tiles over a uniform batch whose
 // utterances span at least a block of rows (a 256-row tile then touches at most two), no padded
-// k-tiles, a gate tail of whole 1-KB DMA pieces per utterance that fits the 32 KB behind the stages.
+// k-tiles, a gate tail of whole k-tile groups (128 columns) whose 1-KB DMA pieces per utterance fit the
+// 32 KB behind the stages.
 bool g256_gate_supported(const ConvGemmArgs& p) {
   if (!p.gate || !g256_supported(p) || !uniform_ktiles(p)) return false;
   const bool dense = p.taps == 1 && p.pad == 0 && p.stride == 1 && !p.iseg && !p.seg && p.Ti == p.T;
@@ -427,7 +431,8 @@ void t_g256(const ConvGemmArgs& p, const __bf16* h, const __bf16* l, hipStream_t
   const int am = !uniform_ktiles(p) ? 2 : dense ? 1 : 0;
   if (p.gate) {
     WSP_CHECK(g256_gate_supported(p), "conv_gemm_x3: the gated A tail needs a dense 1x1 GEMM over a uniform batch");
-    const int ldsg = std::max(lds, 2 * kGStage + 2 * (p.K - p.gate_k0) * 4);  // the two gate rows behind the stages
+    // the two gate rows behind the stages, each in whole 1-KB pieces (the kernel's g_slot)
+    const int ldsg = std::max(lds, 2 * kGStage + 2 * (((p.K - p.gate_k0) * 4 + 1023) & ~1023));
     hipLaunchKernelGGL((conv_gemm_g<4, false>), dim3(nwg), dim3(512), ldsg, s, p, h, l);
     WSP_HIP(hipGetLastError());
     return;

@@ -20,7 +20,7 @@ struct Res2Args {
   const float* bias;
   const float* scale;
   const float* shift;
-  int variant;  // 0 / 2 / 3: 128-row windows (halo recompute); 4: strips (w = 128, else as 3)
+  int variant;  // 0 / 2 / 3: 128-row windows (halo recompute); 4: strips (w = 128 only, else refused)
 };
 bool res2_chain_supported(int w, int dil);
 int res2_chain_rout(int dil, int variant, int M);  // output rows per block

@@ -613,6 +613,8 @@ void launch_res2_w(const Res2Args& p, int nblk, hipStream_t s) {
 void launch_res2_chain(const Res2Args& p, int w, hipStream_t s) {
   WSP_CHECK(res2_chain_supported(w, p.dil), "res2_chain: width must be 64 or 128 and dilation 1..4");
   WSP_CHECK(p.M > 0 && (p.seg || p.T > 0), "res2_chain: empty shape");
+  // strips exist for w = 128 only: a 128-row window cannot own a strip's rows
+  WSP_CHECK(p.variant != 4 || w == 128, "res2_chain: variant 4 (strips) needs w = 128");
   WSP_CHECK(p.rout == res2_chain_rout(p.dil, p.variant, p.M), "res2_chain: rout must be res2_chain_rout(dil, variant, M)");
   WSP_CHECK((long long)p.M * p.ldx * 4 < (long long)kOOB && (long long)p.M * p.ldo * 4 < (long long)kOOB,
             "res2_chain: operand exceeds 2 GiB (split the batch)");

@@ -145,7 +145,10 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
  * every utterance of a ragged batch (only the total is checked; a shorter utterance
  * gets an undefined embedding),
  * "XI_VEC_ECAPA_TDNN_c512", "XI_VEC_ECAPA_TDNN_c1024" (the ECAPA trunk with XI
- * pooling and a 1536-wide head; emb_bn optional, no two_emb_layer, >= 1 frame)
+ * pooling and a 1536-wide head; emb_bn optional, no two_emb_layer, >= 1 frame),
+ * "ReDimNetB2" (feat_dim 72 only, ASTP pooling with global context,
+ * two_emb_layer optional, no emb_bn, >= 2 frames; the other ReDimNet sizes are
+ * unsupported archs)
  * (wespeaker/models/speaker_model.py:30-57), or the SSL front end
  * "HuBERT_base" or "WavLM_base" (feat_dim 1, embed_dim 768;
  * wespeaker/frontend/s3prl.py:23-75).  "WavLM_base" is s3prl's wavlm_base /

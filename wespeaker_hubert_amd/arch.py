@@ -61,6 +61,17 @@ GEMINI_ARCHS = {
 GEMINI_DIMS = (32, 32, 64, 128, 256)
 GEMINI_STRIDE_T = (1, 2, 1, 1)  # Golden Gemini T14c: the frequency stride is 2 at every level
 
+REDIMNET_ARCHS = {
+    # name: (C, group_divisor, stages) with a stage = (frequency stride, 2-D ConvNeXt blocks, 1-D block
+    # reduction 1152 / hC) — redimnet.py:924-947: convnext_like 2-D blocks, "conv+att" 1-D blocks
+    "ReDimNetB2": (16, 4, ((1, 2, 12), (2, 2, 12), (1, 3, 12), (2, 4, 8), (1, 4, 8), (2, 4, 4))),
+}
+# the constructors the path refuses by name (other block types, group sizes, a stride-3 stage)
+REDIMNET_OTHERS = ("ReDimNetB0", "ReDimNetB1", "ReDimNetB3", "ReDimNetB4", "ReDimNetB5", "ReDimNetB6")
+REDIMNET_FEAT = 72
+REDIMNET_DW_KERNELS = (7, 19, 31, 59)  # the four depthwise convs of a 1-D block (redimnet.py:584-607)
+REDIMNET_HEADS = 4
+
 XVEC_ARCHS = {
     # name: default pooling_func — tdnn.py:57-118, xi_vector.py XI_VEC_XVEC
     "XVEC": "TSTP",
@@ -105,13 +116,18 @@ class ModelSpec:
             return "eres2net"
         if self.arch in GEMINI_ARCHS:
             return "gemini"
+        if self.arch in REDIMNET_ARCHS:
+            return "redimnet"
         raise KeyError(self.arch)
 
 
 def check_arch(arch: str) -> None:
     """Unknown names raise (the reference prints and exit(1)s, speaker_model.py:55-57)."""
+    if arch in REDIMNET_OTHERS:
+        raise NotImplementedError(f"{arch}: the ReDimNet path implements ReDimNetB2 (the voxceleb/v2 recipe); the other "
+                                  "sizes need other block types, group sizes and a stride-3 stage")
     known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS, XVEC_ARCHS,
-             XI_ECAPA_ARCHS)
+             XI_ECAPA_ARCHS, REDIMNET_ARCHS)
     if not any(arch in k for k in known):
         raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
 
@@ -135,6 +151,19 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
                 raise NotImplementedError(f"XVEC path implements {key}={want} (the recipe configuration)")
         if spec.feat_dim < 4 or spec.feat_dim % 4:
             raise ValueError("XVEC feat_dim must be a positive multiple of 4")
+        spec.extra = kw
+        return spec
+    if arch in REDIMNET_ARCHS:
+        # ReDimNetB2(feat_dim=72, embed_dim=192, pooling_func='ASTP', two_emb_layer=False) (redimnet.py:924)
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", REDIMNET_FEAT)), embed_dim=int(kw.pop("embed_dim", 192)),
+                         pooling_func=kw.pop("pooling_func", "ASTP"),
+                         two_emb_layer=bool(kw.pop("two_emb_layer", False)))
+        if "emb_bn" in kw:  # the constructor has none (a TypeError there too)
+            raise TypeError("ReDimNetB2 has no emb_bn")
+        if spec.pooling_func != "ASTP":
+            raise NotImplementedError("ReDimNet path implements ASTP pooling (the recipe configuration)")
+        if spec.feat_dim != REDIMNET_FEAT:
+            raise ValueError("ReDimNet path implements feat_dim=72 (the recipe configuration: C * F = 1152)")
         spec.extra = kw
         return spec
     if arch in XI_ECAPA_ARCHS:
@@ -457,7 +486,63 @@ def gemini_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def redimnet_stage_dims(arch: str):
+    """Per stage (c_in, F_in, stride, c, F, blocks, hC): the 2-D view going in, after the entry conv,
+    and the 1-D block's hidden width."""
+    C, _, stages = REDIMNET_ARCHS[arch]
+    c, F, out = C, REDIMNET_FEAT, []
+    for s, n, red in stages:
+        out.append((c, F, s, c * s, F // s, n, C * REDIMNET_FEAT // red))
+        c, F = c * s, F // s
+    return out
+
+
+def redimnet_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of ReDimNetB2 (redimnet.py:622-871): the input weights of the six stages and
+    of the output, the stem, per stage the entry conv, its 2-D ConvNeXt blocks and the 1-D block
+    (reduction + LayerNorm, four depthwise ConvNeXt blocks, the transformer layer, expansion), then
+    the ASTP pooling (global context) and seg_1 (+ seg_bn_1 / seg_2)."""
+    C, gd, stages = REDIMNET_ARCHS[spec.arch]
+    D = C * spec.feat_dim
+    out: ParamList = [("backbone.inputs_weights.0", (1, 1, 1, 1))]
+    out += [(f"backbone.inputs_weights.{i}", (1, i + 1, D, 1)) for i in range(1, len(stages) + 1)]
+    out += [("backbone.stem.0.weight", (C, 1, 3, 3)), ("backbone.stem.0.bias", (C,)),
+            ("backbone.stem.1.weight", (C,)), ("backbone.stem.1.bias", (C,))]
+    for si, (ci, _, s, c, _, n, hC) in enumerate(redimnet_stage_dims(spec.arch)):
+        p = f"backbone.stage{si}"
+        out += [(f"{p}.0.weight", (c, ci, s, 1)), (f"{p}.0.bias", (c,))]
+        for bi in range(1, n + 1):
+            q = f"{p}.{bi}.conv_block"
+            out += [(q + ".dwconvs.0.weight", (c, gd, 3, 3)), (q + ".dwconvs.0.bias", (c,))] + _bn(q + ".norm", c)
+            out += [(q + ".pwconv1.weight", (c, c, 1, 1)), (q + ".pwconv1.bias", (c,))]
+        q = f"{p}.{n + 2}"  # index n + 1 is to1d, which has no parameters
+        out += [(q + ".red_dim_conv.0.weight", (hC, D, 1)), (q + ".red_dim_conv.0.bias", (hC,)),
+                (q + ".red_dim_conv.1.weight", (hC,)), (q + ".red_dim_conv.1.bias", (hC,))]
+        for j, k in enumerate(REDIMNET_DW_KERNELS):
+            r = f"{q}.tcm.{j}"
+            out += [(r + ".dwconvs.0.weight", (hC, 1, k)), (r + ".dwconvs.0.bias", (hC,))] + _bn(r + ".norm", hC)
+            out += [(r + ".pwconv1.weight", (hC, hC, 1)), (r + ".pwconv1.bias", (hC,))]
+        r = f"{q}.tcm.4"
+        for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            out += [(f"{r}.attention.{proj}.weight", (hC, hC)), (f"{r}.attention.{proj}.bias", (hC,))]
+        out += [(r + ".layer_norm.weight", (hC,)), (r + ".layer_norm.bias", (hC,))]
+        for lin in ("intermediate_dense", "output_dense"):
+            out += [(f"{r}.feed_forward.{lin}.weight", (hC, hC)), (f"{r}.feed_forward.{lin}.bias", (hC,))]
+        out += [(r + ".final_layer_norm.weight", (hC,)), (r + ".final_layer_norm.bias", (hC,))]
+        out += [(q + ".exp_dim_conv.weight", (D, hC, 1)), (q + ".exp_dim_conv.bias", (D,))]
+    out += [("pool.linear1.weight", (128, 3 * D, 1)), ("pool.linear1.bias", (128,)),
+            ("pool.linear2.weight", (D, 128, 1)), ("pool.linear2.bias", (D,))]
+    out += [("seg_1.weight", (spec.embed_dim, 2 * D)), ("seg_1.bias", (spec.embed_dim,))]
+    if spec.two_emb_layer:
+        out += [("seg_bn_1.running_mean", (spec.embed_dim,)), ("seg_bn_1.running_var", (spec.embed_dim,)),
+                ("seg_bn_1.num_batches_tracked", ()),
+                ("seg_2.weight", (spec.embed_dim, spec.embed_dim)), ("seg_2.bias", (spec.embed_dim,))]
+    return out
+
+
 def param_list(spec: ModelSpec) -> ParamList:
+    if spec.family == "redimnet":
+        return redimnet_params(spec)
     if spec.family == "xvec":
         return xvec_params(spec)
     if spec.family == "gemini":
@@ -570,6 +655,21 @@ def gemini_gflop_per_utt(spec: ModelSpec, T: int) -> float:
         d = dims[li + 1]
         macs += F * t * (9 * dims[li] * d + n * (8 * d * d + 36 * d))
     macs += 2 * F * dims[4] * spec.embed_dim
+    return 2.0 * macs / 1e9
+
+
+def redimnet_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one ReDimNetB2 forward over T frames: the stem, per stage the
+    entry conv, the 2-D blocks (grouped 3x3 + 1x1), the 1-D block (reduction, four depthwise + 1x1
+    blocks, the six hC x hC linears, attention's two T x T products, expansion), pool.linear1 / 2
+    and seg_1 (+ seg_2)."""
+    C, gd, _ = REDIMNET_ARCHS[spec.arch]
+    D = C * spec.feat_dim
+    macs = T * D * 9
+    for ci, _, s, c, _, n, hC in redimnet_stage_dims(spec.arch):
+        macs += T * D * (s * ci + n * (9 * gd + c))
+        macs += T * (2 * D * hC + sum(REDIMNET_DW_KERNELS) * hC + 4 * hC * hC + 6 * hC * hC) + 2 * T * T * hC
+    macs += T * 2 * D * 128 + 2 * D * 128 + 2 * D * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
     return 2.0 * macs / 1e9
 
 

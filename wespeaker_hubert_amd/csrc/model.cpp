@@ -3,7 +3,7 @@
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
 // The families derive from Model::Impl: their tables, folds, workspace layouts and forward
 // schedules are in ecapa_model.cpp, resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp,
-// campplus_model.cpp, eres2net_model.cpp, gemini_model.cpp and xvec_model.cpp; Model::create below is the one place here that names them.
+// campplus_model.cpp, eres2net_model.cpp, gemini_model.cpp, xvec_model.cpp and redimnet_model.cpp; Model::create below is the one place here that names them.
 #include "model_impl.h"
 
 namespace wsp {
@@ -175,7 +175,8 @@ Model::~Model() { delete impl; }
 
 void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
   WSP_CHECK(!impl, "model already created");
-  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec})
+  for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec,
+                         make_redimnet})
     if ((impl = make(arch, feat_dim, embed_dim, emb_bn, two_emb))) break;
   WSP_CHECK(impl, "unsupported arch " + arch);
   // Creation and parameter intake are host-only; the device is bound at

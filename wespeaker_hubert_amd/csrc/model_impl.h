@@ -6,6 +6,7 @@
 //   hubert_model.cpp  Hubert    campplus_model.cpp  Campplus
 //   eres2net_model.cpp  Eres2Net  gemini_model.cpp  Gemini
 //   xvec_model.cpp    Xvec (XVEC with TSTP, XI_VEC_XVEC with XI pooling)
+//   redimnet_model.cpp  Redimnet (ReDimNetB2)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -269,6 +270,6 @@ struct Model::Impl {
 // One per family, defined beside its subclass: the arch names the family serves, their argument
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
-MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec;
+MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec, make_redimnet;
 
 }  // namespace wsp

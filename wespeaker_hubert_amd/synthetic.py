@@ -41,6 +41,8 @@ def synth_param(seed: int, name: str, shape: Tuple[int, ...]) -> np.ndarray:
         return (0.5 * rng.standard_normal(shape)).astype(np.float32)
     if leaf == "prior_logprec":
         return rng.standard_normal(shape).astype(np.float32)
+    if "inputs_weights" in name:  # ReDimNet's per-channel softmax logits: O(1), so that the softmax is far from uniform
+        return rng.standard_normal(shape).astype(np.float32)
     if name.endswith("featurizer.weights"):
         return (0.5 * rng.standard_normal(shape)).astype(np.float32)
     is_norm = (".bn" in name or name.startswith("bn") or ".norm" in name

@@ -21,7 +21,7 @@ FILL = 0x7FC5A5A5  # the NaN pattern result buffers are pre-filled with
 # the runner's own in a result record, result arrays of a case that ran (None: their number is in the file).
 LAYOUT = {"conv_gemm_run": (43, 7, 3), "cam_dense_run": (8, 0, 2), "eres2net_run": (16, 0, 1),
           "gemini_run": (16, 0, 1), "ssl_run": (16, 0, None), "xi_run": (8, 0, 1),
-          "ecapa_run": (16, 2, None)}
+          "ecapa_run": (16, 2, None), "resnet_run": (16, 0, None)}
 
 
 def untouched(x):

@@ -134,6 +134,7 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
  * multiple of 8, TSTP pooling, no emb_bn / two_emb_layer, >= 3 frames),
  * "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug" (feat_dim a multiple
  * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames),
+ * "Res2Net34_Base", "Res2Net34_Large" (the same conditions as ERes2Net),
  * "Gemini_DF_ResNet60/114/183/237" (feat_dim a multiple of 16, TSTP pooling,
  * two_emb_layer optional, no emb_bn, >= 3 frames),
  * "XVEC" (the x-vector TDNN with TSTP pooling, >= 16 frames) and "XI_VEC_XVEC"
@@ -244,6 +245,11 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *                  depthwise conv's output inside conv3's operand (no 4d-wide intermediate; slower
  *                  as measured, kept for A/B runs).  Equal up to fp32 rounding; the workspace
  *                  follows the value, so query its size after setting it
+ *   "res2_tail"    Res2Net handles only: the tail of a block behind conv1 (the 3x3 conv of the first
+ *                  channel slice, conv3 over [its output | the second slice], residual, clamp).
+ *                  0 = two launches, the 3x3 conv's output through memory; 2 = one launch in every
+ *                  stage, that output kept in registers; 1 (default) = one launch in the stages where
+ *                  it measured faster, two in the others.  Equal up to fp32 rounding
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block

@@ -51,6 +51,15 @@ ERES2NET_ARCHS = {
 }
 ERES2NET_BLOCKS = (3, 4, 6, 3)
 
+RES2NET_ARCHS = {
+    # name: m_channels — res2net.py:192-211; BasicBlockRes2Net: expansion 2, baseWidth 32, scale 2 (the
+    # constructors cannot change any of them), num_blocks (3, 4, 6, 3)
+    "Res2Net34_Base": 32,
+    "Res2Net34_Large": 64,
+}
+RES2NET_BLOCKS = (3, 4, 6, 3)
+RES2NET_EXPANSION, RES2NET_SCALE = 2, 2
+
 GEMINI_ARCHS = {
     # name: depths — gemini_dfresnet.py:145-178 (the downsample layers count as layers)
     "Gemini_DF_ResNet60": (3, 3, 9, 3),
@@ -102,6 +111,8 @@ class ModelSpec:
 
     @property
     def family(self) -> str:
+        if self.arch in RES2NET_ARCHS:  # before anything that matches by prefix
+            return "res2net"
         if self.arch.startswith("ECAPA_TDNN") or self.arch in XI_ECAPA_ARCHS:
             return "ecapa"
         if self.arch in XVEC_ARCHS:
@@ -127,7 +138,7 @@ def check_arch(arch: str) -> None:
         raise NotImplementedError(f"{arch}: the ReDimNet path implements ReDimNetB2 (the voxceleb/v2 recipe); the other "
                                   "sizes need other block types, group sizes and a stride-3 stage")
     known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS, XVEC_ARCHS,
-             XI_ECAPA_ARCHS, REDIMNET_ARCHS)
+             XI_ECAPA_ARCHS, REDIMNET_ARCHS, RES2NET_ARCHS)
     if not any(arch in k for k in known):
         raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
 
@@ -188,6 +199,21 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
         if spec.feat_dim < 16 or spec.feat_dim % 16:
             # gemini_dfresnet.py:63 sizes seg_1 for int(feat_dim / 16) rows while level 4 keeps ceil(feat_dim / 16)
             raise ValueError("Gemini DF-ResNet feat_dim must be a positive multiple of 16")
+        spec.extra = kw
+        return spec
+    if arch in RES2NET_ARCHS:
+        # Res2Net34_*(feat_dim, embed_dim, pooling_func='TSTP', two_emb_layer=False): no defaults for the
+        # first two in the reference; the project's 80 / 192
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 192)),
+                         pooling_func=kw.pop("pooling_func", "TSTP"),
+                         two_emb_layer=bool(kw.pop("two_emb_layer", False)), m_channels=RES2NET_ARCHS[arch])
+        if "emb_bn" in kw:  # the constructor has none (a TypeError there too)
+            raise TypeError("Res2Net has no emb_bn")
+        if spec.pooling_func != "TSTP":
+            raise NotImplementedError("Res2Net path implements TSTP pooling (the recipe configuration)")
+        if spec.feat_dim < 8 or spec.feat_dim % 8:
+            # res2net.py:110 sizes seg_1 for int(feat_dim / 8) rows while stage 4 keeps ceil(feat_dim / 8)
+            raise ValueError("Res2Net feat_dim must be a positive multiple of 8")
         spec.extra = kw
         return spec
     if arch in ERES2NET_ARCHS:
@@ -463,6 +489,39 @@ def eres2net_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def res2net_blocks(spec: ModelSpec):
+    """(prefix, in_planes, planes, width, stride, has_shortcut) of every block (res2net.py:34-155)."""
+    m, exp = RES2NET_ARCHS[spec.arch], RES2NET_EXPANSION
+    in_planes = m
+    for li, n in enumerate(RES2NET_BLOCKS):
+        planes = m * (2 ** li)
+        for bi in range(n):
+            stride = 2 if (li > 0 and bi == 0) else 1
+            yield (f"layer{li + 1}.{bi}", in_planes, planes, planes // 2, stride,
+                   stride != 1 or in_planes != exp * planes)
+            in_planes = exp * planes
+
+
+def res2net_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of Res2Net (res2net.py:34-147): stem, the blocks (conv1, the one 3x3 conv of the
+    scale-2 chain, conv3, the projection shortcut of a stage's first block), seg_1 (+ seg_bn_1 / seg_2)."""
+    m, exp = RES2NET_ARCHS[spec.arch], RES2NET_EXPANSION
+    out: ParamList = [("conv1.weight", (m, 1, 3, 3))] + _bn("bn1", m)
+    for p, in_planes, planes, w, stride, has_sc in res2net_blocks(spec):
+        out += [(p + ".conv1.weight", (2 * w, in_planes, 1, 1))] + _bn(p + ".bn1", 2 * w)
+        out += [(p + ".convs.0.weight", (w, w, 3, 3))] + _bn(p + ".bns.0", w)
+        out += [(p + ".conv3.weight", (planes * exp, 2 * w, 1, 1))] + _bn(p + ".bn3", planes * exp)
+        if has_sc:
+            out += [(p + ".shortcut.0.weight", (planes * exp, in_planes, 1, 1))] + _bn(p + ".shortcut.1", planes * exp)
+    stats_dim = int(spec.feat_dim / 8) * m * 8 * exp
+    out += [("seg_1.weight", (spec.embed_dim, stats_dim * 2)), ("seg_1.bias", (spec.embed_dim,))]
+    if spec.two_emb_layer:
+        out += [("seg_bn_1.running_mean", (spec.embed_dim,)), ("seg_bn_1.running_var", (spec.embed_dim,)),
+                ("seg_bn_1.num_batches_tracked", ()),
+                ("seg_2.weight", (spec.embed_dim, spec.embed_dim)), ("seg_2.bias", (spec.embed_dim,))]
+    return out
+
+
 def gemini_params(spec: ModelSpec) -> ParamList:
     """state_dict layout of Gemini_DF_ResNet (gemini_dfresnet.py:51-103): every downsample layer (0 is
     the stem) first, then the inverted bottlenecks stage by stage, then seg_1."""
@@ -541,6 +600,8 @@ def redimnet_params(spec: ModelSpec) -> ParamList:
 
 
 def param_list(spec: ModelSpec) -> ParamList:
+    if spec.family == "res2net":
+        return res2net_params(spec)
     if spec.family == "redimnet":
         return redimnet_params(spec)
     if spec.family == "xvec":
@@ -640,6 +701,21 @@ def eres2net_gflop_per_utt(spec: ModelSpec, T: int) -> float:
         ci, co, n = c * 2 ** (i - 1), c * 2 ** i, pos[f"layer{i + 1}"]
         macs += n * (9 * ci * co + 2 * co * (co // 4) + (co // 4) * co)
     macs += 2 * c * 8 * F * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
+    return 2.0 * macs / 1e9
+
+
+def res2net_gflop_per_utt(spec: ModelSpec, T: int) -> float:
+    """Algorithmic FLOPs (2 x MACs) of one Res2Net forward over T frames: stem, every block's conv1,
+    3x3 conv, conv3 and projection shortcut, seg_1 (+ seg_2)."""
+    m, exp = RES2NET_ARCHS[spec.arch], RES2NET_EXPANSION
+    F, t = spec.feat_dim, T
+    macs = F * t * m * 9
+    for p, in_planes, planes, w, stride, has_sc in res2net_blocks(spec):
+        F, t = (F - 1) // stride + 1, (t - 1) // stride + 1
+        macs += F * t * (in_planes * 2 * w + 9 * w * w + 2 * w * planes * exp)
+        if has_sc:
+            macs += F * t * in_planes * planes * exp
+    macs += 2 * m * exp * 8 * F * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
     return 2.0 * macs / 1e9
 
 

@@ -24,6 +24,10 @@ enum EresAct { kEresNone = 0, kEresRelu = 1, kEresClamp = 2 };  // clamp: min(ma
 // channel offsets multiples of 4 floats.  w = pack::frag16(W [N][taps cin]), bias = [N].
 // out / res point at the first channel written / read (row strides ldo / ldres): only columns
 // [0, N) of rows [0, M) are written.
+// launch_eres_pw with ksplit > 0 reads a concatenated operand instead of an added one: input channel
+// k < ksplit is a[row][k], channel k >= ksplit is a2[row][k - ksplit] (row stride lda2); ksplit a
+// multiple of 8 below cin, so a lane's eight consecutive k stay in one source (Res2Net's conv3 over
+// [S | Y1[:, w:]]).  0 = off.
 struct EresConvArgs {
   const float* a;
   int lda;
@@ -38,6 +42,7 @@ struct EresConvArgs {
   float* out;
   int ldo;
   int act;
+  int ksplit = 0;
 };
 bool eres_conv3x3_supported(int width);  // 16, 24, 32, 48, 64, 96, 128, 192, 256
 void launch_eres_conv3x3(const EresConvArgs& p, hipStream_t s);

@@ -11,7 +11,10 @@
 // so a lane ends up with four consecutive output channels of one position.  eres_conv_kernel is
 // the implicit GEMM over taps x cin (the 3x3 Res2 step and, with one tap, the 1x1 convs with their
 // 2-D stride gather, residual and clamp); weight fragments come straight from global memory (they
-// are at most a few hundred KB and stay in L2).  eres_aff_kernel keeps the AFF's hidden row
+// are at most a few hundred KB and stay in L2); with EresConvArgs::ksplit the 1x1 conv reads a
+// concatenated operand, channels below ksplit from a and the rest from a2 (Res2Net's conv3: a k-step
+// lies in one source where ksplit % 32 == 0, else a lane loads from both, one of them out of range).
+// eres_aff_kernel keeps the AFF's hidden row
 // (C / 4 channels) in accumulators: two stacked 16-channel tiles are exactly one 32-long k-step
 // of the second product's B operand, in the k order pack::frag16(acc_order) gives its weights.
 #include "eres2net.h"
@@ -82,6 +85,26 @@ __global__ __launch_bounds__(256) void eres_conv_kernel(const EresConvArgs p, co
       const int fi = fi0[pt] + kf, ti = ti0[pt] + kt;
       const bool ok = live[pt] && kin && fi >= 0 && fi < p.Fi && ti >= 0 && ti < p.Ti;
       const int row = ok ? ib[pt] + fi * p.Ti + ti : 0;
+      if (TAPS == 1 && p.ksplit > 0 && (p.ksplit & 31) == 0) {  // concatenated operand, a k-step in one source
+        if (32 * ks < p.ksplit) {                                 // (wave-uniform)
+          const int off = ok ? (row * p.lda + c) * 4 : kOOB;
+          v[pt][0] = bload4(ra, off);
+          v[pt][1] = bload4(ra, ok ? off + 16 : kOOB);
+        } else {
+          const int off = ok ? (row * p.lda2 + c - p.ksplit) * 4 : kOOB;
+          v[pt][0] = bload4(ra2, off);
+          v[pt][1] = bload4(ra2, ok ? off + 16 : kOOB);
+        }
+        continue;
+      }
+      if (TAPS == 1 && p.ksplit > 0) {  // the split inside a k-step: both loads, one of them out of range (zeros)
+        const bool lo = c < p.ksplit;
+        const int off = ok && lo ? (row * p.lda + c) * 4 : kOOB;
+        const int off2 = ok && !lo ? (row * p.lda2 + c - p.ksplit) * 4 : kOOB;
+        v[pt][0] = bload4(ra, off) + bload4(ra2, off2);
+        v[pt][1] = bload4(ra, ok && lo ? off + 16 : kOOB) + bload4(ra2, ok && !lo ? off2 + 16 : kOOB);
+        continue;
+      }
       const int off = ok ? (row * p.lda + c) * 4 : kOOB;
       v[pt][0] = bload4(ra, off);
       v[pt][1] = bload4(ra, ok ? off + 16 : kOOB);
@@ -266,8 +289,14 @@ void launch_conv(const EresConvArgs& p, int taps, hipStream_t s) {
   WSP_CHECK(p.B > 0 && p.Fi > 0 && p.Ti > 0 && p.cin > 0 && p.N > 0 && (p.stride == 1 || p.stride == 2),
             "eres_conv: bad shape");
   WSP_CHECK(p.cin % 8 == 0 && p.N % 4 == 0, "eres_conv: cin % 8 == 0 and N % 4 == 0");
-  WSP_CHECK(p.lda >= p.cin && p.lda % 4 == 0 && p.ldo >= p.N && p.ldo % 4 == 0, "eres_conv: bad strides");
-  WSP_CHECK(!p.a2 || (p.lda2 >= p.cin && p.lda2 % 4 == 0), "eres_conv: bad stride of the added slice");
+  WSP_CHECK(p.lda >= (p.ksplit > 0 ? 8 : p.cin) && p.lda % 4 == 0 && p.ldo >= p.N && p.ldo % 4 == 0, "eres_conv: bad strides");
+  WSP_CHECK(p.ksplit == 0 || taps == 1, "eres_conv: ksplit goes with the 1x1 conv only");
+  WSP_CHECK(p.ksplit == 0 || (p.ksplit > 0 && p.ksplit % 8 == 0 && p.ksplit < p.cin),
+            "eres_conv: ksplit must be a multiple of 8 below cin");
+  WSP_CHECK(p.ksplit == 0 || p.a2, "eres_conv: ksplit needs the second operand a2");
+  WSP_CHECK(!p.a2 || (p.lda2 >= (p.ksplit ? p.cin - p.ksplit : p.cin) && p.lda2 % 4 == 0),
+            "eres_conv: bad stride of the added slice");
+  WSP_CHECK(p.ksplit == 0 || p.lda >= p.ksplit, "eres_conv: bad strides");
   WSP_CHECK(!p.res || (p.ldres >= p.N && p.ldres % 4 == 0), "eres_conv: bad residual stride");
   WSP_CHECK(aligned16(p.a) && aligned16(p.a2) && aligned16(p.w) && aligned16(p.bias) && aligned16(p.res) &&
                 aligned16(p.out) && p.bias && p.w && p.a && p.out,
@@ -319,13 +348,14 @@ bool eres_conv3x3_supported(int w) {
 }
 
 void launch_eres_conv3x3(const EresConvArgs& p, hipStream_t s) {
+  WSP_CHECK(p.ksplit == 0, "eres_conv3x3: ksplit goes with the 1x1 conv only");
   WSP_CHECK(eres_conv3x3_supported(p.cin) && p.N == p.cin && p.stride == 1,
             "eres_conv3x3: stride 1, width in {16, 24, 32, 48, 64, 96, 128, 192, 256}");
   launch_conv(p, 9, s);
 }
 
 void launch_eres_pw(const EresConvArgs& p, hipStream_t s) {
-  WSP_CHECK(!p.a2, "eres_pw: no added slice");
+  WSP_CHECK(!p.a2 || p.ksplit != 0, "eres_pw: no added slice");
   launch_conv(p, 1, s);
 }
 

@@ -9,6 +9,7 @@
 // data: Base, Large and aug share every line below.
 #include "eres2net.h"
 #include "model_impl.h"
+#include "pw_fold.h"
 
 namespace wsp {
 
@@ -19,11 +20,6 @@ struct Eres2Net final : Model::Impl {
   using Impl::Impl;
   int m = 32, base_width = 32, scale = 2, expansion = 2;
   float *stem_w = nullptr, *stem_b = nullptr;  // conv1 + bn1
-  struct Pw {  // BN-folded conv as pack::frag16 fragments + bias
-    void* w = nullptr;
-    float* b = nullptr;
-    int N = 0, K = 0;
-  };
   struct Aff {  // both BatchNorms folded into the convs
     int C = 0;
     void *wa = nullptr, *wb = nullptr;
@@ -49,7 +45,6 @@ struct Eres2Net final : Model::Impl {
 
   void build_params() override;
   void add_aff(const std::string& p, int C);
-  Pw fold_pw(const std::string& wname, const std::string& bn, int N, int cin, int taps);
   Aff fold_aff(const std::string& p, int C);
   void finalize() override;
   void check_forward(int B, int T) const override;
@@ -150,18 +145,6 @@ void Eres2Net::build_params() {
   }
 }
 
-// conv [N][cin][taps] -> BN folded, k = tap * cin + c, as eres2net.hip fragments
-Eres2Net::Pw Eres2Net::fold_pw(const std::string& wname, const std::string& bn, int N, int cin, int taps) {
-  const Folded f = fold_bn(wname, bn);
-  Pw pw;
-  pw.N = N;
-  pw.K = cin * taps;
-  const std::vector<float> wk = pack::conv_kmajor(f.w, N, cin, taps, pw.K);
-  pw.w = dev.upload_u16(pack::frag16(wk.data(), N, pw.K, pw.K));
-  pw.b = dev.upload(f.b);
-  return pw;
-}
-
 // BN(conv(x) + bias) = (W s) x + (bias s + shift), for both convs of local_att
 Eres2Net::Aff Eres2Net::fold_aff(const std::string& p, int C) {
   WSP_CHECK(eres_aff_supported(C), "ERes2Net: no AFF kernel for " + std::to_string(C) + " channels");
@@ -199,18 +182,18 @@ void Eres2Net::finalize() {
     const std::string& p = b.name;
     const int w = b.width;
     WSP_CHECK(eres_conv3x3_supported(w), "ERes2Net: no 3x3 kernel for width " + std::to_string(w));
-    b.c1 = fold_pw(p + ".conv1.weight", p + ".bn1", w * scale, b.in_planes, 1);
+    b.c1 = fold_pw(*this, p + ".conv1.weight", p + ".bn1", w * scale, b.in_planes, 1);
     for (int i = 0; i < scale; ++i) {
       if (b.aff && i == 0) {
-        b.convs.push_back(fold_pw(p + ".conv2_1.weight", p + ".bn2_1", w, w, 9));
+        b.convs.push_back(fold_pw(*this, p + ".conv2_1.weight", p + ".bn2_1", w, w, 9));
         continue;
       }
       const std::string n = std::to_string(b.aff ? i - 1 : i);
-      b.convs.push_back(fold_pw(p + ".convs." + n + ".weight", p + ".bns." + n, w, w, 9));
+      b.convs.push_back(fold_pw(*this, p + ".convs." + n + ".weight", p + ".bns." + n, w, w, 9));
       if (b.aff) b.affs.push_back(fold_aff(p + ".fuse_models." + n, w));
     }
-    b.c3 = fold_pw(p + ".conv3.weight", p + ".bn3", b.out_planes, w * scale, 1);
-    if (b.has_sc) b.sc = fold_pw(p + ".shortcut.0.weight", p + ".shortcut.1", b.out_planes, b.in_planes, 1);
+    b.c3 = fold_pw(*this, p + ".conv3.weight", p + ".bn3", b.out_planes, w * scale, 1);
+    if (b.has_sc) b.sc = fold_pw(*this, p + ".shortcut.0.weight", p + ".shortcut.1", b.out_planes, b.in_planes, 1);
   }
   const int c = m * expansion;
   static const char* kFuse[3] = {"fuse_mode12", "fuse_mode123", "fuse_mode1234"};

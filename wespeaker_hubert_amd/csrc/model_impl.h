@@ -6,7 +6,7 @@
 //   hubert_model.cpp  Hubert    campplus_model.cpp  Campplus
 //   eres2net_model.cpp  Eres2Net  gemini_model.cpp  Gemini
 //   xvec_model.cpp    Xvec (XVEC with TSTP, XI_VEC_XVEC with XI pooling)
-//   redimnet_model.cpp  Redimnet (ReDimNetB2)
+//   redimnet_model.cpp  Redimnet (ReDimNetB2)   res2net_model.cpp  Res2Net
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -169,6 +169,11 @@ struct Options {
   // launches (the family's default: measured faster); 1 = conv1 + the fused tail (depthwise 3x3
   // inside the 1x1 projection's operand)
   int ib_fused = 0;
+  // Res2Net: the tail of a block behind conv1 (3x3 conv of the first slice, conv3 over the
+  // concatenation, residual).  0 = two launches (launch_eres_conv3x3, launch_eres_pw with ksplit);
+  // 1 = one launch (res2net.hip) in the stages where it measured faster (res2net_model.cpp);
+  // 2 = one launch in every stage (A/B runs)
+  int res2_tail = 1;
 };
 
 struct Model::Impl {
@@ -270,6 +275,7 @@ struct Model::Impl {
 // One per family, defined beside its subclass: the arch names the family serves, their argument
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
-MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec, make_redimnet;
+MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec, make_redimnet,
+    make_res2net;
 
 }  // namespace wsp

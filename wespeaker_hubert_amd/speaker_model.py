@@ -184,7 +184,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Gemini DF-ResNet / x-vector / ReDimNetB2 speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Res2Net / Gemini DF-ResNet / x-vector / ReDimNetB2 speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -269,8 +269,9 @@ class HipSpeakerModel(_HipHandle):
         # as does ERes2Net.forward (eres2net.py:380-391); Gemini_DF_ResNet.forward returns
         # (tensor(0.), embed) like ResNet (gemini_dfresnet.py:129-141); XVEC.forward returns
         # (embed_a, embed_b) and outputs[-1] = embed_b is the embedding (tdnn.py:109-118); ReDimNet.forward
-        # returns (tensor(0.), embed_a) or (embed_a, embed_b) (redimnet.py:860-871): outputs[-1] either way
-        if self.spec.family in ("simam", "campplus", "eres2net"):
+        # returns (tensor(0.), embed_a) or (embed_a, embed_b) (redimnet.py:860-871): outputs[-1] either way;
+        # Res2Net.forward returns the embedding itself (res2net.py:178-189)
+        if self.spec.family in ("simam", "campplus", "eres2net", "res2net"):
             return self.embed(feats)
         return None, self.embed(feats)
 

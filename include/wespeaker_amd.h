@@ -135,6 +135,15 @@ int wsp_fbank_segments(const void* wav, int wav_dtype, int B, const int32_t* sam
  * "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug" (feat_dim a multiple
  * of 8, TSTP pooling, two_emb_layer optional, no emb_bn, >= 9 frames),
  * "Res2Net34_Base", "Res2Net34_Large" (the same conditions as ERes2Net),
+ * "REPVGG_TINY_A0", "REPVGG_A0", "REPVGG_A1", "REPVGG_A2", "REPVGG_B0" and the
+ * RepSPK variants "REPVGG_TINY_RSBB_A0", "REPVGG_RSBB_A0", "REPVGG_RSBB_A2",
+ * "REPVGG_RSBB_B0" (feat_dim a multiple of 8, TSTP pooling, >= 9 frames; emb_bn and
+ * two_emb_layer are refused: the constructors have neither; the other REPVGG_*
+ * names are unsupported archs).  A RepVGG handle knows the re-parameterised
+ * ("deploy") layout only: per block stage0 / stage{1..4}.{i} it takes
+ * rbr_reparam.weight (out, in, k, k), k = 3 or, for RepSPK, 5, and rbr_reparam.bias,
+ * then seg.weight / seg.bias.  A training-form checkpoint is folded by the host
+ * (the Python package's arch.repvgg_fold, bin/convert_repvgg.py) before it is set,
  * "Gemini_DF_ResNet60/114/183/237" (feat_dim a multiple of 16, TSTP pooling,
  * two_emb_layer optional, no emb_bn, >= 3 frames),
  * "XVEC" (the x-vector TDNN with TSTP pooling, >= 16 frames) and "XI_VEC_XVEC"
@@ -250,6 +259,14 @@ int wsp_model_forward_segments(wsp_model* m, const float* feats, int B, const in
  *                  0 = two launches, the 3x3 conv's output through memory; 2 = one launch in every
  *                  stage, that output kept in registers; 1 (default) = one launch in the stages where
  *                  it measured faster, two in the others.  Equal up to fp32 rounding
+ *   "rsbb_taps"    RepVGG handles only; RepSPK blocks (the *_RSBB_* names), whose folded 5x5 kernel
+ *                  is zero at 8 of its 25 taps.  2 = every block runs the 17 live taps only
+ *                  (repvgg.hip: K = 17 cin, the dead taps neither loaded nor multiplied); 0 = all
+ *                  25 taps on the 2-D implicit GEMM; 1 (default) = the 17 taps in the stages where
+ *                  that measured faster (all of them).  A block whose loaded weight is non-zero at
+ *                  one of the eight taps runs all 25 whatever the value.  The stem runs its 17 (or
+ *                  25) taps in f32 FMAs either way.  Bit-identical results.  precision 0 is refused
+ *                  on RepVGG handles, as on the ResNets
  *   "in_planes"    SimAM-ResNet, before the weights: 32 or 64
  *   "attn_pipe"    HuBERT front end: 1 = the persistent pipelined attention kernel (keys in
  *                  LDS halves of 128 frames, the next half in flight; default), 0 = one block

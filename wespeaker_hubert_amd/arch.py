@@ -81,6 +81,34 @@ REDIMNET_FEAT = 72
 REDIMNET_DW_KERNELS = (7, 19, 31, 59)  # the four depthwise convs of a 1-D block (redimnet.py:584-607)
 REDIMNET_HEADS = 4
 
+REPVGG_ARCHS = {
+    # name: (block kind, blocks per stage, stage-0 width, stage widths) — repvgg.py:602-747.  Strides are
+    # (1, 1, 2, 2, 2) throughout; stage-0 width = min(64, int(64 * width_multiplier[0])); a RepSPK block
+    # (the *_RSBB_* names) has a dilation-2 3x3 branch where a RepVGG block has its 1x1 branch
+    "REPVGG_TINY_A0": ("RepVGG", (3, 4, 23, 3), 32, (32, 64, 128, 256)),
+    "REPVGG_TINY_RSBB_A0": ("RepSPK", (3, 4, 23, 3), 32, (32, 64, 128, 256)),
+    "REPVGG_A0": ("RepVGG", (2, 4, 14, 1), 48, (48, 96, 192, 1280)),
+    "REPVGG_RSBB_A0": ("RepSPK", (2, 4, 14, 1), 48, (48, 96, 192, 1280)),
+    "REPVGG_A1": ("RepVGG", (2, 4, 14, 1), 64, (64, 128, 256, 1280)),
+    "REPVGG_A2": ("RepVGG", (2, 4, 14, 1), 64, (96, 192, 384, 1408)),
+    "REPVGG_RSBB_A2": ("RepSPK", (2, 4, 14, 1), 64, (96, 192, 384, 1408)),
+    "REPVGG_B0": ("RepVGG", (4, 6, 16, 1), 64, (64, 128, 256, 1280)),
+    "REPVGG_RSBB_B0": ("RepSPK", (4, 6, 16, 1), 64, (64, 128, 256, 1280)),
+}
+# the constructors the path refuses by name, with the reason
+REPVGG_OTHERS = {
+    **{n: "stage-4 widths of 2048 / 2560" for n in ("REPVGG_B1", "REPVGG_B2", "REPVGG_B3")},
+    **{n: "grouped convs" for n in ("REPVGG_B1g2", "REPVGG_B1g4", "REPVGG_B2g2", "REPVGG_B2g4", "REPVGG_B3g2",
+                                    "REPVGG_B3g4")},
+    "REPVGG_D2SE": "grouped convs and the 2-D SE block",
+}
+REPVGG_STRIDES = (1, 2, 2, 2)  # of stages 1..4 (stage0: 1)
+# The 17 live taps (kf, kt) of a folded RepSPK 5x5 kernel, row-major: {kf, kt both even} (the dilated 3x3) and
+# {1 <= kf, kt <= 3} (the plain 3x3), sharing the centre.  The other eight are structurally zero.
+RSBB_LIVE_TAPS = tuple((kf, kt) for kf in range(5) for kt in range(5)
+                       if (kf % 2 == 0 and kt % 2 == 0) or (1 <= kf <= 3 and 1 <= kt <= 3))
+RSBB_DEAD_TAPS = tuple((kf, kt) for kf in range(5) for kt in range(5) if (kf, kt) not in RSBB_LIVE_TAPS)
+
 XVEC_ARCHS = {
     # name: default pooling_func — tdnn.py:57-118, xi_vector.py XI_VEC_XVEC
     "XVEC": "TSTP",
@@ -108,11 +136,14 @@ class ModelSpec:
     two_emb_layer: bool = False
     m_channels: int = 32
     extra: dict = field(default_factory=dict)
+    deploy: bool = False  # RepVGG: the state_dict layout (False: training branches, True: rbr_reparam)
 
     @property
     def family(self) -> str:
         if self.arch in RES2NET_ARCHS:  # before anything that matches by prefix
             return "res2net"
+        if self.arch in REPVGG_ARCHS:
+            return "repvgg"
         if self.arch.startswith("ECAPA_TDNN") or self.arch in XI_ECAPA_ARCHS:
             return "ecapa"
         if self.arch in XVEC_ARCHS:
@@ -137,8 +168,11 @@ def check_arch(arch: str) -> None:
     if arch in REDIMNET_OTHERS:
         raise NotImplementedError(f"{arch}: the ReDimNet path implements ReDimNetB2 (the voxceleb/v2 recipe); the other "
                                   "sizes need other block types, group sizes and a stride-3 stage")
+    if arch in REPVGG_OTHERS:
+        raise NotImplementedError(f"{arch}: the RepVGG path implements the TINY_A0 / A0 / A1 / A2 / B0 sizes and their "
+                                  f"RSBB variants; {arch} needs {REPVGG_OTHERS[arch]}")
     known = (ECAPA_ARCHS, RESNET_ARCHS, SIMAM_ARCHS, CAMPP_ARCHS, ERES2NET_ARCHS, GEMINI_ARCHS, XVEC_ARCHS,
-             XI_ECAPA_ARCHS, REDIMNET_ARCHS, RES2NET_ARCHS)
+             XI_ECAPA_ARCHS, REDIMNET_ARCHS, RES2NET_ARCHS, REPVGG_ARCHS)
     if not any(arch in k for k in known):
         raise KeyError(f"{arch} not found !!! (supported: {sum((sorted(k) for k in known), [])})")
 
@@ -199,6 +233,26 @@ def make_spec(arch: str, **model_args) -> ModelSpec:
         if spec.feat_dim < 16 or spec.feat_dim % 16:
             # gemini_dfresnet.py:63 sizes seg_1 for int(feat_dim / 16) rows while level 4 keeps ceil(feat_dim / 16)
             raise ValueError("Gemini DF-ResNet feat_dim must be a positive multiple of 16")
+        spec.extra = kw
+        return spec
+    if arch in REPVGG_ARCHS:
+        # REPVGG_*(feat_dim, embed_dim, pooling_func='TSTP', deploy=False, use_se=False): no defaults for the
+        # first two in the reference; 80 / 256 (the recipes' values)
+        spec = ModelSpec(arch=arch, feat_dim=int(kw.pop("feat_dim", 80)), embed_dim=int(kw.pop("embed_dim", 256)),
+                         pooling_func=kw.pop("pooling_func", "TSTP"), deploy=bool(kw.pop("deploy", False)))
+        for key in ("emb_bn", "two_emb_layer"):  # the constructors have neither (a TypeError there too)
+            if key in kw:
+                raise TypeError(f"RepVGG has no {key}")
+        if kw.pop("use_se", False):
+            raise NotImplementedError("RepVGG path implements use_se=False (the recipe configuration); the 2-D SE block "
+                                      "is not implemented")
+        if spec.pooling_func != "TSTP":
+            raise NotImplementedError("RepVGG path implements TSTP pooling (the recipe configuration)")
+        if spec.feat_dim < 8 or spec.feat_dim % 8:
+            # repvgg.py:520 sizes the pooling for int(feat_dim / 8) rows while stage 4 keeps ceil(feat_dim / 8)
+            raise ValueError("RepVGG feat_dim must be a positive multiple of 8")
+        if spec.embed_dim < 1:
+            raise ValueError("RepVGG embed_dim must be positive")
         spec.extra = kw
         return spec
     if arch in RES2NET_ARCHS:
@@ -522,6 +576,113 @@ def res2net_params(spec: ModelSpec) -> ParamList:
     return out
 
 
+def repvgg_blocks(spec: ModelSpec):
+    """(prefix, stage 0..4, cin, cout, stride, has_identity) of every block (repvgg.py:456-554); stage0 is
+    the 1 -> C0 stem, itself a block of the family's kind."""
+    _, nblocks, c0, widths = REPVGG_ARCHS[spec.arch]
+    yield ("stage0", 0, 1, c0, 1, False)
+    cin = c0
+    for li, n in enumerate(nblocks):
+        for bi in range(n):
+            stride = REPVGG_STRIDES[li] if bi == 0 else 1
+            yield (f"stage{li + 1}.{bi}", li + 1, cin, widths[li], stride, cin == widths[li] and stride == 1)
+            cin = widths[li]
+
+
+def repvgg_kernel_size(spec: ModelSpec) -> int:
+    """Side of a block's folded kernel: 3 (RepVGG), 5 (RepSPK)."""
+    return 5 if REPVGG_ARCHS[spec.arch][0] == "RepSPK" else 3
+
+
+def repvgg_params(spec: ModelSpec) -> ParamList:
+    """state_dict layout of RepVGG (repvgg.py:105-554) in the form `spec.deploy` selects.  Training form
+    (avg_model.pt): per block the identity BatchNorm (where cin == cout and stride 1), rbr_dense.{conv, bn}
+    and rbr_1x1.{conv, bn} (RepSPK: rbr_dense_dilation in its place).  Deploy form (convert_model.pt): per
+    block rbr_reparam.{weight [cout, cin, k, k], bias}, k = 3 or 5.  Then seg."""
+    spk = REPVGG_ARCHS[spec.arch][0] == "RepSPK"
+    k = repvgg_kernel_size(spec)
+    out: ParamList = []
+    cout = 0
+    for p, _, cin, cout, _, has_id in repvgg_blocks(spec):
+        if spec.deploy:
+            out += [(p + ".rbr_reparam.weight", (cout, cin, k, k)), (p + ".rbr_reparam.bias", (cout,))]
+            continue
+        if has_id:
+            out += _bn(p + ".rbr_identity", cin)
+        out += [(p + ".rbr_dense.conv.weight", (cout, cin, 3, 3))] + _bn(p + ".rbr_dense.bn", cout)
+        if spk:
+            out += [(p + ".rbr_dense_dilation.conv.weight", (cout, cin, 3, 3))] + _bn(p + ".rbr_dense_dilation.bn", cout)
+        else:
+            out += [(p + ".rbr_1x1.conv.weight", (cout, cin, 1, 1))] + _bn(p + ".rbr_1x1.bn", cout)
+    stats_dim = cout * int(spec.feat_dim / 8)
+    out += [("seg.weight", (spec.embed_dim, 2 * stats_dim)), ("seg.bias", (spec.embed_dim,))]
+    return out
+
+
+def repvgg_fold(spec: ModelSpec, state_dict) -> dict:
+    """Training-form state_dict -> deploy-form state_dict (float32 numpy, repvgg_params(deploy=True) order),
+    computed in float64.  Every branch's eval BatchNorm (eps 1e-5) is folded into its kernel,
+        K' = K * g / sqrt(v + eps) per output channel,   b' = beta - mean * g / sqrt(v + eps),
+    and the branches are summed into one k x k kernel: RepVGG (k = 3) the 3x3 kernel plus the 1x1 kernel at
+    the centre tap; RepSPK (k = 5) the 3x3 kernel at the inner taps 1..3 plus the dilation-2 3x3 kernel at
+    the even taps 0, 2, 4; the identity BatchNorm as a centre-tap diagonal.  The eight taps of a RepSPK
+    kernel that no branch reaches are exact zeros."""
+    import numpy as np
+
+    def get(name):
+        v = state_dict[name]
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        return np.asarray(v, dtype=np.float64)
+
+    def affine(p):
+        t = get(p + ".weight") / np.sqrt(get(p + ".running_var") + 1e-5)
+        return t, get(p + ".bias") - get(p + ".running_mean") * t
+
+    spk = REPVGG_ARCHS[spec.arch][0] == "RepSPK"
+    k = repvgg_kernel_size(spec)
+    c = k // 2
+    out = {}
+    for p, _, cin, cout, _, has_id in repvgg_blocks(spec):
+        kern = np.zeros((cout, cin, k, k), dtype=np.float64)
+        t, bias = affine(p + ".rbr_dense.bn")
+        kern[:, :, c - 1:c + 2, c - 1:c + 2] += get(p + ".rbr_dense.conv.weight") * t[:, None, None, None]
+        if spk:
+            t, b = affine(p + ".rbr_dense_dilation.bn")
+            kern[:, :, ::2, ::2] += get(p + ".rbr_dense_dilation.conv.weight") * t[:, None, None, None]
+        else:
+            t, b = affine(p + ".rbr_1x1.bn")
+            kern[:, :, c, c] += get(p + ".rbr_1x1.conv.weight")[:, :, 0, 0] * t[:, None]
+        bias = bias + b
+        if has_id:
+            t, b = affine(p + ".rbr_identity")
+            kern[np.arange(cout), np.arange(cin), c, c] += t
+            bias = bias + b
+        out[p + ".rbr_reparam.weight"] = kern.astype(np.float32)
+        out[p + ".rbr_reparam.bias"] = bias.astype(np.float32)
+    for name in ("seg.weight", "seg.bias"):
+        out[name] = get(name).astype(np.float32)
+    return out
+
+
+def repvgg_dense_blocks(spec: ModelSpec, deploy_state_dict) -> tuple:
+    """The RepSPK blocks (prefixes) of a deploy-form state_dict whose rbr_reparam.weight is non-zero at any
+    of the eight dead taps: the library runs those on the dense 25-tap path, whatever `rsbb_taps` says
+    (a hand-edited or fine-tuned deploy checkpoint; the converter's output has none)."""
+    import numpy as np
+    if repvgg_kernel_size(spec) != 5:
+        return ()
+    dead = []
+    for p, *_ in repvgg_blocks(spec):
+        w = deploy_state_dict[p + ".rbr_reparam.weight"]
+        if hasattr(w, "detach"):
+            w = w.detach().cpu().numpy()
+        w = np.asarray(w)
+        if any(np.any(w[:, :, kf, kt] != 0) for kf, kt in RSBB_DEAD_TAPS):
+            dead.append(p)
+    return tuple(dead)
+
+
 def gemini_params(spec: ModelSpec) -> ParamList:
     """state_dict layout of Gemini_DF_ResNet (gemini_dfresnet.py:51-103): every downsample layer (0 is
     the stem) first, then the inverted bottlenecks stage by stage, then seg_1."""
@@ -602,6 +763,8 @@ def redimnet_params(spec: ModelSpec) -> ParamList:
 def param_list(spec: ModelSpec) -> ParamList:
     if spec.family == "res2net":
         return res2net_params(spec)
+    if spec.family == "repvgg":
+        return repvgg_params(spec)
     if spec.family == "redimnet":
         return redimnet_params(spec)
     if spec.family == "xvec":
@@ -716,6 +879,22 @@ def res2net_gflop_per_utt(spec: ModelSpec, T: int) -> float:
         if has_sc:
             macs += F * t * in_planes * planes * exp
     macs += 2 * m * exp * 8 * F * spec.embed_dim + (spec.embed_dim ** 2 if spec.two_emb_layer else 0)
+    return 2.0 * macs / 1e9
+
+
+def repvgg_gflop_per_utt(spec: ModelSpec, T: int, rsbb_taps: int = 1, dense_blocks=()) -> float:
+    """FLOPs (2 x MACs) one RepVGG forward over T frames executes: every block as its one folded conv
+    (9 taps; a RepSPK block 17 taps on the sparse path, rsbb_taps = 1, and 25 on the dense path,
+    rsbb_taps = 0 or a block named in `dense_blocks`, see repvgg_dense_blocks), then seg.  The dense figure of
+    a RepSPK model, repvgg_gflop_per_utt(spec, T, 0), is 25 / 17 of the sparse one in the convs.  Channel
+    padding (widths 48 and 96 run as 64 and 128) is not counted."""
+    k = repvgg_kernel_size(spec)
+    F, t, macs, cout = spec.feat_dim, T, 0, 0
+    for p, _, cin, cout, stride, _ in repvgg_blocks(spec):
+        F, t = (F - 1) // stride + 1, (t - 1) // stride + 1
+        taps = 9 if k == 3 else (17 if rsbb_taps and p not in dense_blocks else 25)
+        macs += F * t * cout * cin * taps
+    macs += 2 * cout * F * spec.embed_dim
     return 2.0 * macs / 1e9
 
 

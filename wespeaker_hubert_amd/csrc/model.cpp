@@ -3,7 +3,7 @@
 // the host in f64), the implicit-GEMM launch helpers, sub-batch streams, options and profiling.
 // The families derive from Model::Impl: their tables, folds, workspace layouts and forward
 // schedules are in ecapa_model.cpp, resnet_model.cpp (ResNet and SimAM-ResNet), hubert_model.cpp,
-// campplus_model.cpp, eres2net_model.cpp, gemini_model.cpp, xvec_model.cpp, redimnet_model.cpp and res2net_model.cpp; Model::create below is the one place here that names them.
+// campplus_model.cpp, eres2net_model.cpp, gemini_model.cpp, xvec_model.cpp, redimnet_model.cpp, res2net_model.cpp and repvgg_model.cpp; Model::create below is the one place here that names them.
 #include "model_impl.h"
 
 namespace wsp {
@@ -176,7 +176,7 @@ Model::~Model() { delete impl; }
 void Model::create(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb) {
   WSP_CHECK(!impl, "model already created");
   for (MakeImpl* make : {make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec,
-                         make_redimnet, make_res2net})
+                         make_redimnet, make_res2net, make_repvgg})
     if ((impl = make(arch, feat_dim, embed_dim, emb_bn, two_emb))) break;
   WSP_CHECK(impl, "unsupported arch " + arch);
   // Creation and parameter intake are host-only; the device is bound at
@@ -307,6 +307,8 @@ const Opt kOpts[] = {
     {"ib_fused", &I::ib_fused, 0, 1, kNoHole, "ib_fused must be 0 (conv1, depthwise conv, conv3) or 1 (conv1, fused tail)"},
     {"res2_tail", &I::res2_tail, 0, 2, kNoHole,
      "res2_tail must be 0 (3x3 conv, then conv3), 1 (fused tail where it measured faster) or 2 (fused tail everywhere)"},
+    {"rsbb_taps", &I::rsbb_taps, 0, 2, kNoHole,
+     "rsbb_taps must be 0 (dense 25-tap conv), 1 (17 live taps where it measured faster) or 2 (17 live taps everywhere)"},
     {"cat_gate", &I::cat_gate, 0, 1, kNoHole, "cat_gate must be 0 or 1"},
     {"gate_fold", &I::gate_fold, 0, 1, kNoHole, "gate_fold must be 0 or 1"},
     {"seam_fold", &I::seam_fold, 0, 1, kNoHole, "seam_fold must be 0 or 1"},
@@ -352,6 +354,8 @@ void Model::set_option(const std::string& key, int value) {
     for (const auto& p : m.params) WSP_CHECK(!p.set, "option 'in_planes' must be set before the weights");
   } else if (key == "res2_tail") {
     WSP_CHECK(m.owns_option(key), "option 'res2_tail' applies to Res2Net handles");
+  } else if (key == "rsbb_taps") {
+    WSP_CHECK(m.owns_option(key), "option 'rsbb_taps' applies to RepVGG handles");
   }
   WSP_CHECK(value >= o.lo && value <= o.hi && value != o.hole, o.err);
   if (key == "x3_variant") {

@@ -7,6 +7,7 @@
 //   eres2net_model.cpp  Eres2Net  gemini_model.cpp  Gemini
 //   xvec_model.cpp    Xvec (XVEC with TSTP, XI_VEC_XVEC with XI pooling)
 //   redimnet_model.cpp  Redimnet (ReDimNetB2)   res2net_model.cpp  Res2Net
+//   repvgg_model.cpp  RepVgg (RepVGG and RepSPK blocks, deploy form)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -174,6 +175,10 @@ struct Options {
   // 1 = one launch (res2net.hip) in the stages where it measured faster (res2net_model.cpp);
   // 2 = one launch in every stage (A/B runs)
   int res2_tail = 1;
+  // RepVGG with RepSPK blocks (the *_RSBB_* names): the folded 5x5 conv of a block.  0 = all 25 taps
+  // through the 2-D implicit GEMM; 2 = the 17 live taps (repvgg.hip) in every block whose eight dead taps
+  // are zero; 1 = the 17 live taps in the stages where that measured faster (repvgg_model.cpp)
+  int rsbb_taps = 1;
 };
 
 struct Model::Impl {
@@ -276,6 +281,6 @@ struct Model::Impl {
 // checks and per-arch option defaults.  Null: not one of that family's archs.
 using MakeImpl = Model::Impl*(const std::string& arch, int feat_dim, int embed_dim, bool emb_bn, bool two_emb);
 MakeImpl make_ecapa, make_resnet, make_hubert, make_campplus, make_eres2net, make_gemini, make_xvec, make_redimnet,
-    make_res2net;
+    make_res2net, make_repvgg;
 
 }  // namespace wsp

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arch import ModelSpec, check_arch, make_spec, param_list, xvec_handle_arch, xvec_min_frames
+from .arch import ModelSpec, check_arch, make_spec, param_list, repvgg_fold, xvec_handle_arch, xvec_min_frames
 
 logger = logging.getLogger(__name__)
 
@@ -107,9 +107,15 @@ class _HipHandle:
             self._device = idx
         return self
 
+    def _device_host(self) -> Dict[str, np.ndarray]:
+        """The tensors the library takes, keyed by its parameter names (the loaded ones, unless a subclass
+        re-parameterises them on the way)."""
+        return self._host
+
     def _build(self):
         lib = _lib.load()
         h = ctypes.c_void_p()
+        host = self._device_host()
         arch, feat_dim, embed_dim, emb_bn, two_emb = self._create_args()
         _lib.check(lib.wsp_model_create(arch.encode(), feat_dim, embed_dim, int(emb_bn), int(two_emb),
                                         ctypes.byref(h)), "wsp_model_create")
@@ -127,9 +133,9 @@ class _HipHandle:
                 want = tuple(shape[d] for d in range(ndim.value))
                 if key.endswith("num_batches_tracked"):
                     continue
-                if key not in self._host:
+                if key not in host:
                     raise RuntimeError(f"parameter {key} was not loaded (shape {want})")
-                arr = np.ascontiguousarray(self._host[key], dtype=np.float32)
+                arr = np.ascontiguousarray(host[key], dtype=np.float32)
                 if tuple(arr.shape) != want:
                     raise RuntimeError(f"{key}: shape {arr.shape} != {want}")
                 _lib.check(lib.wsp_model_set_param(h, i, arr.ctypes.data, arr.size), "set_param " + key)
@@ -184,7 +190,7 @@ class _HipHandle:
 
 
 class HipSpeakerModel(_HipHandle):
-    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Res2Net / Gemini DF-ResNet / x-vector / ReDimNetB2 speaker backbone executed by hand-written gfx950 kernels."""
+    """ECAPA-TDNN / ResNet / SimAM-ResNet / CAM++ / ERes2Net / Res2Net / Gemini DF-ResNet / x-vector / ReDimNetB2 / RepVGG speaker backbone executed by hand-written gfx950 kernels."""
 
     def __init__(self, arch: str, **model_args):
         super().__init__()
@@ -198,6 +204,16 @@ class HipSpeakerModel(_HipHandle):
         s = self.spec
         arch = xvec_handle_arch(s) if s.family == "xvec" else s.arch  # (XVEC, pooling_func='XI') = XI_VEC_XVEC
         return arch, s.feat_dim, s.embed_dim, s.emb_bn, s.two_emb_layer
+
+    def _device_host(self):
+        # RepVGG: the library knows the deploy layout only; a training-form model (deploy=False, what
+        # avg_model.pt holds) is folded on the host, in float64, when it goes to the device
+        if self.spec.family != "repvgg" or self.spec.deploy:
+            return self._host
+        for key, shape in self._layout:
+            if key not in self._host and not key.endswith("num_batches_tracked"):
+                raise RuntimeError(f"parameter {key} was not loaded (shape {tuple(shape)})")
+        return repvgg_fold(self.spec, self._host)
 
     # ----------------------------------------------------------- forward --
     def workspace_bytes(self, B: int, T: int) -> int:
@@ -270,8 +286,9 @@ class HipSpeakerModel(_HipHandle):
         # (tensor(0.), embed) like ResNet (gemini_dfresnet.py:129-141); XVEC.forward returns
         # (embed_a, embed_b) and outputs[-1] = embed_b is the embedding (tdnn.py:109-118); ReDimNet.forward
         # returns (tensor(0.), embed_a) or (embed_a, embed_b) (redimnet.py:860-871): outputs[-1] either way;
-        # Res2Net.forward returns the embedding itself (res2net.py:178-189)
-        if self.spec.family in ("simam", "campplus", "eres2net", "res2net"):
+        # Res2Net.forward returns the embedding itself (res2net.py:178-189), as does RepVGG.forward
+        # (repvgg.py:582-587)
+        if self.spec.family in ("simam", "campplus", "eres2net", "res2net", "repvgg"):
             return self.embed(feats)
         return None, self.embed(feats)
 
